@@ -8,6 +8,10 @@ Driver contract:
 launched for N>1 as torch.distributed.run with one rank per GPU; reads
 RANK/LOCAL_RANK/WORLD_SIZE/MASTER_* from env; rank 0 prints ONE JSON line
 with the whole-job aggregate tokens/s.
+
+A plain run sets up, warms up, times K steps and prints that line.
+--dump-outputs DIR also writes the last timed step's results as .npy;
+--full adds the auxiliary measurements (launch->first-step latency).
 """
 
 from __future__ import annotations
@@ -19,6 +23,31 @@ import sys
 import time
 
 import torch
+
+
+DUMP_SAMPLE = 1 << 20  # elements kept per dumped buffer (4 MiB as f32)
+
+
+def dump_outputs(out_dir: str, loss: float, flat) -> None:
+    """Write the last timed step's results as float32 .npy files: the loss
+    it returned, and per param group the updated params and the grads it
+    left behind.  Buffers larger than DUMP_SAMPLE are sampled at fixed
+    seeded positions, so two builds dump the same elements."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "loss.npy"),
+            np.asarray([loss], dtype=np.float32))
+    for group, p16, grad in flat.groups():
+        n = p16.numel()
+        idx = None
+        if n > DUMP_SAMPLE:
+            pos = np.random.default_rng(0).integers(0, n, size=DUMP_SAMPLE)
+            idx = torch.from_numpy(np.sort(pos)).to(p16.device)
+        for name, buf in (("params", p16), ("grads", grad)):
+            sel = buf if idx is None else buf[idx]
+            np.save(os.path.join(out_dir, f"{name}_{group}.npy"),
+                    sel.detach().float().cpu().numpy())
 
 
 def main() -> int:
@@ -49,7 +78,15 @@ def main() -> int:
                    choices=["auto", "on", "off"],
                    help="also measure launch->first-step latency through the "
                         "full dist.ddp launcher path (the other half of the "
-                        "BASELINE metric); auto = on for 1-GPU runs")
+                        "BASELINE metric); auto = on for 1-GPU runs with "
+                        "--full")
+    p.add_argument("--full", action="store_true",
+                   help="also run the auxiliary measurements a plain run "
+                        "skips (launch->first-step latency)")
+    p.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                   help="after the timed steps, write what the last step "
+                        "produced (loss, seeded samples of the updated "
+                        "params and of the grads) as DIR/<name>.npy")
     args = p.parse_args()
 
     rank = int(os.environ.get("RANK", "0"))
@@ -252,12 +289,15 @@ def main() -> int:
     peak_hbm_gb = (round(torch.cuda.max_memory_allocated() / 1e9, 2)
                    if use_gpu else None)
 
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, loss, flat)
+
     # launch->first-step latency (the other half of the BASELINE metric):
     # the full dist.ddp launcher path — materialize -> Popen -> agent ->
     # c10d rendezvous -> RCCL init -> first fwd+bwd+step (1x1, gpu_tiny)
     launch_latency = None
     measure_latency = (args.launch_latency == "on"
-                       or (args.launch_latency == "auto"
+                       or (args.launch_latency == "auto" and args.full
                            and world == 1 and use_gpu))
     if measure_latency and rank == 0:
         try:

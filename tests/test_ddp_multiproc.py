@@ -318,3 +318,45 @@ def test_bench_contract_world2_cpu(tmp_path):
     assert result["n_gpus"] == 2
     assert result["value"] > 0
     assert result["config"]["parallelism"] == "dp2"
+
+
+def _bench_tiny_cpu(*extra):
+    env = dict(os.environ)
+    env["PYTHONPATH"] = str(REPO) + os.pathsep + env.get("PYTHONPATH", "")
+    out = subprocess.run(
+        [sys.executable, str(REPO / "bench.py"), "--gpus", "1",
+         "--steps", "2", "--warmup", "1", "--model", "tiny",
+         "--device", "cpu", *extra],
+        env=env, cwd=str(REPO), capture_output=True, text=True, timeout=300,
+    )
+    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, out.stdout
+    return json.loads(lines[0])
+
+
+def test_bench_dump_outputs_reproducible(tmp_path):
+    """--dump-outputs writes the last timed step's results as float .npy
+    files, and two runs with the same arguments dump the same arrays."""
+    import numpy as np
+
+    dumps = []
+    for name in ("a", "b"):
+        out_dir = tmp_path / name
+        result = _bench_tiny_cpu("--dump-outputs", str(out_dir))
+        assert result["steps"] == 2
+        assert result["ms_per_step"] > 0
+        # a plain run carries no auxiliary measurement
+        assert "launch_to_first_step_s" not in result
+        arrays = {f.stem: np.load(f) for f in sorted(out_dir.glob("*.npy"))}
+        assert {"loss", "params_decay", "grads_decay"} <= set(arrays)
+        for arr in arrays.values():
+            assert arr.dtype in (np.float32, np.float64)
+            assert np.isfinite(arr).all()
+        assert arrays["loss"][0] == np.float32(result["config"]["final_loss"])
+        assert np.abs(arrays["grads_decay"]).max() > 0
+        assert sum(a.nbytes for a in arrays.values()) <= 64 * 2**20
+        dumps.append(arrays)
+    assert dumps[0].keys() == dumps[1].keys()
+    for name in dumps[0]:
+        np.testing.assert_array_equal(dumps[0][name], dumps[1][name])

@@ -58,6 +58,29 @@ def test_rmsnorm_fwd_bwd(dev):
     assert rel_err(w.grad, wr.grad) < 3e-2
 
 
+@pytest.mark.parametrize("rows,H", [(3, 2048), (64, 2048), (1000, 4096),
+                                    (129, 6144)])
+def test_rmsnorm_bwd_dw_reproducible(dev, rows, H):
+    """dw is reduced over row chunks in a fixed order: repeated calls agree
+    bit for bit (rows below, at and off the 64-row chunk size, one to three
+    2048-column tiles), and match an fp64 sum within fp32 accumulation
+    error: each of the `rows` adds/fmas rounds by at most 2^-24 relative to
+    a running sum bounded by sum|terms|, doubled for the product rounding."""
+    hip = _hip().hip_ops()
+    x = torch.randn(rows, H, device=dev, dtype=torch.bfloat16)
+    w = torch.randn(H, device=dev, dtype=torch.bfloat16)
+    dy = torch.randn(rows, H, device=dev, dtype=torch.bfloat16)
+    _, invrms = hip.rmsnorm_fwd(x, w, 1e-5)
+    dws = [hip.rmsnorm_bwd(dy, x, w, invrms)[1] for _ in range(3)]
+    assert dws[0].shape == (H,) and dws[0].dtype == torch.float32
+    assert torch.equal(dws[0], dws[1]) and torch.equal(dws[0], dws[2])
+    terms = dy.double() * x.double() * invrms.double()[:, None]
+    bound = rows * 2.0 ** -23 * terms.abs().sum(0) + 1e-30
+    err = (dws[0].double() - terms.sum(0)).abs()
+    print(f"rows={rows} H={H} max err/bound = {(err / bound).max().item():.3g}")
+    assert (err <= bound).all()
+
+
 def test_rope_fwd_bwd(dev):
     from torchx_amd.ops import reference, rope_tables
 

@@ -78,18 +78,32 @@ def _lin(mod: nn.Module, x: torch.Tensor) -> torch.Tensor:
     return mod(x)
 
 
+def _new_linear(in_features: int, out_features: int,
+                device: Optional[torch.device]) -> nn.Linear:
+    """Bias-free bf16 nn.Linear.  For a GPU model the weight is allocated
+    on the device uninitialized: LlamaModel._init_weights overwrites every
+    Linear weight, and nn.Linear's own init of 8B params on the host (plus
+    the copy over) dominated model construction.  The device RNG stream,
+    and so the initial weights, are the same either way."""
+    if device is not None and torch.device(device).type == "cuda":
+        return torch.nn.utils.skip_init(
+            nn.Linear, in_features, out_features, bias=False,
+            dtype=torch.bfloat16, device=device)
+    return nn.Linear(in_features, out_features, bias=False,
+                     dtype=torch.bfloat16)
+
+
 class LlamaBlock(nn.Module):
-    def __init__(self, cfg: LlamaConfig):
+    def __init__(self, cfg: LlamaConfig,
+                 device: Optional[torch.device] = None):
         super().__init__()
         self.cfg = cfg
         h, qd, kvd = cfg.hidden_size, cfg.q_dim, cfg.kv_dim
         # fused qkv / gate-up projections: one GEMM each
-        self.wqkv = nn.Linear(h, qd + 2 * kvd, bias=False, dtype=torch.bfloat16)
-        self.wo = nn.Linear(qd, h, bias=False, dtype=torch.bfloat16)
-        self.wgu = nn.Linear(h, 2 * cfg.intermediate_size, bias=False,
-                             dtype=torch.bfloat16)
-        self.wdown = nn.Linear(cfg.intermediate_size, h, bias=False,
-                               dtype=torch.bfloat16)
+        self.wqkv = _new_linear(h, qd + 2 * kvd, device)
+        self.wo = _new_linear(qd, h, device)
+        self.wgu = _new_linear(h, 2 * cfg.intermediate_size, device)
+        self.wdown = _new_linear(cfg.intermediate_size, h, device)
         self.attn_norm = nn.Parameter(torch.ones(h, dtype=torch.bfloat16))
         self.mlp_norm = nn.Parameter(torch.ones(h, dtype=torch.bfloat16))
 
@@ -120,13 +134,12 @@ class LlamaModel(nn.Module):
         factory = {"dtype": torch.bfloat16, "device": device}
         self.embed = nn.Embedding(cfg.vocab_size, cfg.hidden_size, **factory)
         self.blocks = nn.ModuleList(
-            [LlamaBlock(cfg) for _ in range(cfg.num_layers)]
+            [LlamaBlock(cfg, device) for _ in range(cfg.num_layers)]
         )
         self.final_norm = nn.Parameter(
             torch.ones(cfg.hidden_size, dtype=torch.bfloat16)
         )
-        self.lm_head = nn.Linear(cfg.hidden_size, cfg.vocab_size, bias=False,
-                                 dtype=torch.bfloat16)
+        self.lm_head = _new_linear(cfg.hidden_size, cfg.vocab_size, device)
         if cfg.tie_embeddings:
             self.lm_head.weight = self.embed.weight
         cos, sin = ops.rope_tables(cfg.max_seq_len, cfg.head_dim,

@@ -14,7 +14,8 @@ void swiglu_bwd_launch(const void*, const void*, const void*, void*, void*,
 void rmsnorm_fwd_launch(const void*, const void*, void*, void*, long, int,
                         float, hipStream_t);
 void rmsnorm_bwd_launch(const void*, const void*, const void*, const void*,
-                        void*, void*, long, int, hipStream_t);
+                        void*, void*, void*, long, int, hipStream_t);
+long rmsnorm_bwd_dw_chunks(long);
 void adamw_launch(void*, void*, const void*, void*, void*, long, float, float,
                   float, float, float, float, float, hipStream_t);
 void ce_fwd_launch(const void*, const void*, void*, void*, long, int,
@@ -95,12 +96,15 @@ std::vector<at::Tensor> rmsnorm_bwd(at::Tensor dy, at::Tensor x, at::Tensor w,
   check_bf16(dy, "dy");
   check_bf16(x, "x");
   const long H = x.size(-1);
+  TORCH_CHECK(H % 2048 == 0 && H <= 8192, "rmsnorm: H must be k*2048, <=8192");
   const long rows = x.numel() / H;
   auto dx = at::empty_like(x);
-  auto dw = at::zeros({H}, x.options().dtype(at::kFloat));
+  auto dw = at::empty({H}, x.options().dtype(at::kFloat));
+  // per-row-chunk partial sums of dw, reduced in a fixed order
+  auto dw_part = at::empty({rmsnorm_bwd_dw_chunks(rows), H}, dw.options());
   rmsnorm_bwd_launch(dy.data_ptr(), x.data_ptr(), w.data_ptr(),
-                     invrms.data_ptr(), dx.data_ptr(), dw.data_ptr(), rows,
-                     (int)H, cur_stream());
+                     invrms.data_ptr(), dx.data_ptr(), dw.data_ptr(),
+                     dw_part.data_ptr(), rows, (int)H, cur_stream());
   return {dx, dw};
 }
 

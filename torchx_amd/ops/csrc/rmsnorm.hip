@@ -58,8 +58,10 @@ rmsnorm_fwd_kernel(
 //   dx: one block per row, exactly the fwd kernel's shape (which runs at
 //       roofline) — no dw bookkeeping, no serial row walk.
 //   dw: column reduction over row chunks, fp32 register accumulators, one
-//       atomicAdd per element per chunk.  Re-reads dy/x (+33 us at the
-//       bench shape) but every CU stays busy.
+//       partial row per chunk, then a small second kernel sums the chunks
+//       in a fixed order (float atomics would make dw, and with it the
+//       whole training run, differ from run to run).  Re-reads dy/x
+//       (+33 us at the bench shape) but every CU stays busy.
 
 template <int ITERS>
 __global__ void __launch_bounds__(256)
@@ -122,7 +124,7 @@ rmsnorm_bwd_dw_kernel(
     const unsigned short* __restrict__ dy,
     const unsigned short* __restrict__ x,
     const float* __restrict__ invrms,
-    float* __restrict__ dw,  // [H] f32, pre-zeroed
+    float* __restrict__ part,  // [row_chunks, H] f32 partial sums
     long rows, int H) {
   const int col = (blockIdx.y * 2048) + threadIdx.x * 8;
   const long row0 = (long)blockIdx.x * DW_CHUNK_ROWS;
@@ -137,8 +139,34 @@ rmsnorm_bwd_dw_kernel(
       acc[j] = fmaf(bf16_to_f32(dv[j]) * bf16_to_f32(xv[j]), r, acc[j]);
     }
   }
+  float* out = part + (long)blockIdx.x * H + col;
   #pragma unroll
-  for (int j = 0; j < 8; ++j) atomicAdd(dw + col + j, acc[j]);
+  for (int j = 0; j < 8; ++j) out[j] = acc[j];
+}
+
+// dw[c] = sum over chunks of part[chunk][c], always in the same order: one
+// block per 64 columns, 4 groups of 64 threads each walk every 4th chunk,
+// then the 4 group sums are combined through LDS.
+__global__ void __launch_bounds__(256)
+rmsnorm_bwd_dw_reduce_kernel(
+    const float* __restrict__ part,  // [row_chunks, H]
+    float* __restrict__ dw,          // [H]
+    int row_chunks, int H) {
+  __shared__ float red[4][64];
+  const int lane = threadIdx.x & 63;
+  const int group = threadIdx.x >> 6;
+  const int col = blockIdx.x * 64 + lane;
+  float s = 0.f;
+  for (int k = group; k < row_chunks; k += 4) s += part[(long)k * H + col];
+  red[group][lane] = s;
+  __syncthreads();
+  if (group == 0) {
+    dw[col] = (red[0][lane] + red[1][lane]) + (red[2][lane] + red[3][lane]);
+  }
+}
+
+extern "C" long rmsnorm_bwd_dw_chunks(long rows) {
+  return (rows + DW_CHUNK_ROWS - 1) / DW_CHUNK_ROWS;
 }
 
 #define DISPATCH_ITERS(H, FN)                                                  \
@@ -164,8 +192,9 @@ extern "C" void rmsnorm_fwd_launch(const void* x, const void* w, void* y,
 
 extern "C" void rmsnorm_bwd_launch(const void* dy, const void* x,
                                    const void* w, const void* invrms, void* dx,
-                                   void* dw, long rows, int H,
+                                   void* dw, void* dw_part, long rows, int H,
                                    hipStream_t stream) {
+  // dw_part: f32 scratch of rmsnorm_bwd_dw_chunks(rows) * H elements
 #define LAUNCH_B(I)                                                            \
   hipLaunchKernelGGL((rmsnorm_bwd_dx_kernel<I>), dim3((int)rows), dim3(256),   \
                      0, stream, (const unsigned short*)dy,                     \
@@ -173,11 +202,15 @@ extern "C" void rmsnorm_bwd_launch(const void* dy, const void* x,
                      (const float*)invrms, (unsigned short*)dx, H)
   DISPATCH_ITERS(H, LAUNCH_B);
 #undef LAUNCH_B
-  const int row_chunks = (int)((rows + DW_CHUNK_ROWS - 1) / DW_CHUNK_ROWS);
-  hipLaunchKernelGGL(rmsnorm_bwd_dw_kernel,
-                     dim3(row_chunks, H / 2048), dim3(256), 0, stream,
-                     (const unsigned short*)dy, (const unsigned short*)x,
-                     (const float*)invrms, (float*)dw, rows, H);
+  const int row_chunks = (int)rmsnorm_bwd_dw_chunks(rows);
+  if (row_chunks > 0) {
+    hipLaunchKernelGGL(rmsnorm_bwd_dw_kernel,
+                       dim3(row_chunks, H / 2048), dim3(256), 0, stream,
+                       (const unsigned short*)dy, (const unsigned short*)x,
+                       (const float*)invrms, (float*)dw_part, rows, H);
+  }
+  hipLaunchKernelGGL(rmsnorm_bwd_dw_reduce_kernel, dim3(H / 64), dim3(256), 0,
+                     stream, (const float*)dw_part, (float*)dw, row_chunks, H);
 }
 
 // Fused residual-add + RMSNorm (decode/inference): s = x + res (the new
