@@ -39,8 +39,14 @@ def main():
     p.add_argument("--iters", type=int, default=20)
     p.add_argument("--mode", type=str, default="both",
                    choices=["fwd", "bwd", "both"])
+    p.add_argument("--dq-mode", type=str, default=None,
+                   choices=["stream", "recompute"],
+                   help="dQ path of the backward (default: the extension's "
+                        "own default, see ops.set_attn_bwd_dq_mode)")
     args = p.parse_args()
     B, S, Hq, Hkv, D = args.B, args.S, args.Hq, args.Hkv, 128
+    if args.dq_mode is not None:
+        ops.set_attn_bwd_dq_mode(args.dq_mode)
 
     dev = torch.device("cuda", 0)
     torch.manual_seed(0)

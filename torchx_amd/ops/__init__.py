@@ -298,6 +298,18 @@ class _FlashAttention(torch.autograd.Function):
         return dq, dk, dv, None, None
 
 
+def set_attn_bwd_dq_mode(mode: str) -> None:
+    """Select the dQ path of the attention backward: "stream" (default; the
+    dkv kernel exports dS and dQ is one streamed GEMM over it) or
+    "recompute" (the dQ kernel rebuilds dS itself).  The initial value comes
+    from TORCHX_AMD_DQ_MODE."""
+    hip_ops().set_attn_bwd_dq_mode(mode)
+
+
+def get_attn_bwd_dq_mode() -> str:
+    return hip_ops().get_attn_bwd_dq_mode()
+
+
 def flash_attention(
     q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
     causal: bool = True, scale: Optional[float] = None,

@@ -26,8 +26,9 @@ void attn_fwd_launch(const void*, const void*, const void*, void*, void*, int,
                      int, int, int, float, int, long, long, hipStream_t);
 void attn_bwd_launch(const void*, const void*, const void*, const void*,
                      const void*, const void*, void*, void*, void*, void*,
-                     int, int, int, int, float, int, long, long, long, long,
-                     hipStream_t);
+                     void*, int, int, int, int, float, int, long, long, long,
+                     long, hipStream_t);
+long attn_bwd_ds_bytes(int, int, int, int);
 void rope_qkv_launch(const void*, void*, const void*, const void*, long, int,
                      long, int, float, hipStream_t);
 void swiglu_gu_fwd_launch(const void*, void*, long, long, hipStream_t);
@@ -205,6 +206,48 @@ std::vector<at::Tensor> attn_fwd(at::Tensor q, at::Tensor k, at::Tensor v,
   return {o, lse};
 }
 
+// dQ path of the attention backward.  "stream": the dkv kernel exports dS
+// into a scratch buffer and dQ is one streamed GEMM over it; "recompute":
+// the dQ kernel rebuilds S, dP and dS itself.  Initial value from
+// TORCHX_AMD_DQ_MODE (default stream); set_attn_bwd_dq_mode switches it at
+// run time so one process can run both.
+int g_dq_stream = -1;
+
+bool dq_stream_mode() {
+  if (g_dq_stream < 0) {
+    const char* e = getenv("TORCHX_AMD_DQ_MODE");
+    g_dq_stream = (e && std::string(e) == "recompute") ? 0 : 1;
+  }
+  return g_dq_stream == 1;
+}
+
+void set_attn_bwd_dq_mode(const std::string& mode) {
+  TORCH_CHECK(mode == "stream" || mode == "recompute",
+              "attn bwd dq mode must be 'stream' or 'recompute', got '",
+              mode, "'");
+  g_dq_stream = (mode == "stream") ? 1 : 0;
+}
+
+std::string get_attn_bwd_dq_mode() {
+  return dq_stream_mode() ? "stream" : "recompute";
+}
+
+// The scratch is transient HBM on top of the saved activations and grows
+// with S^2 (2.2 GB at B=4, Hq=32, S=4096 causal; 4.4 GB at B=2, S=8192).
+// Above 8 GiB — under 3% of the 288 GB of an MI355X — the call takes the
+// recompute kernel, whose memory does not grow with S^2.
+constexpr long kDsScratchCapBytes = 8L << 30;
+
+// dS scratch for one backward call, or an undefined tensor (null pointer)
+// when the recompute path is to run.
+at::Tensor alloc_ds_scratch(const at::Tensor& like, int B, int S, int Hq,
+                            bool causal) {
+  if (!dq_stream_mode()) return at::Tensor();
+  const long bytes = attn_bwd_ds_bytes(B, S, Hq, causal ? 1 : 0);
+  if (bytes > kDsScratchCapBytes) return at::Tensor();
+  return at::empty({bytes}, like.options().dtype(at::kByte));
+}
+
 std::vector<at::Tensor> attn_bwd(at::Tensor q, at::Tensor k, at::Tensor v,
                                  at::Tensor o, at::Tensor dout, at::Tensor lse,
                                  double scale, bool causal) {
@@ -215,9 +258,11 @@ std::vector<at::Tensor> attn_bwd(at::Tensor q, at::Tensor k, at::Tensor v,
   auto dk = at::empty_like(k);
   auto dv = at::empty_like(v);
   auto delta = at::empty({B, Hq, S}, q.options().dtype(at::kFloat));
+  auto ds = alloc_ds_scratch(q, B, S, Hq, causal);
   attn_bwd_launch(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(),
                   dout.data_ptr(), lse.data_ptr(), delta.data_ptr(),
-                  dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), B, S, Hq, Hkv,
+                  dq.data_ptr(), dk.data_ptr(), dv.data_ptr(),
+                  ds.defined() ? ds.data_ptr() : nullptr, B, S, Hq, Hkv,
                   (float)scale, causal ? 1 : 0, (long)Hq * 128,
                   (long)Hkv * 128, (long)Hq * 128, (long)Hkv * 128,
                   cur_stream());
@@ -251,13 +296,15 @@ at::Tensor attn_bwd_qkv(at::Tensor qkv, at::Tensor o, at::Tensor dout,
   const long rs = (Hq + 2 * Hkv) * 128;
   auto dqkv = at::empty_like(qkv);
   auto delta = at::empty({B, Hq, S}, qkv.options().dtype(at::kFloat));
+  auto ds = alloc_ds_scratch(qkv, B, S, (int)Hq, causal);
   const unsigned short* base = (const unsigned short*)qkv.data_ptr();
   unsigned short* dbase = (unsigned short*)dqkv.data_ptr();
   attn_bwd_launch(base, base + Hq * 128, base + (Hq + Hkv) * 128,
                   o.data_ptr(), dout.data_ptr(), lse.data_ptr(),
                   delta.data_ptr(), dbase, dbase + Hq * 128,
-                  dbase + (Hq + Hkv) * 128, B, S, (int)Hq, (int)Hkv,
-                  (float)scale, causal ? 1 : 0, rs, rs, rs, rs,
+                  dbase + (Hq + Hkv) * 128,
+                  ds.defined() ? ds.data_ptr() : nullptr, B, S, (int)Hq,
+                  (int)Hkv, (float)scale, causal ? 1 : 0, rs, rs, rs, rs,
                   cur_stream());
   return dqkv;
 }
@@ -538,6 +585,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("ce_bwd", &ce_bwd);
   m.def("attn_fwd", &attn_fwd);
   m.def("attn_bwd", &attn_bwd);
+  m.def("set_attn_bwd_dq_mode", &set_attn_bwd_dq_mode);
+  m.def("get_attn_bwd_dq_mode", &get_attn_bwd_dq_mode);
   m.def("attn_fwd_qkv", &attn_fwd_qkv);
   m.def("attn_bwd_qkv", &attn_bwd_qkv);
   m.def("rope_qkv", &rope_qkv);
