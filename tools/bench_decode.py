@@ -23,9 +23,18 @@ def main():
     p.add_argument("--new", type=int, default=128)
     p.add_argument("--graph", action="store_true",
                    help="hipGraph decode loop (whole step as one replay)")
+    p.add_argument("--paged", action="store_true",
+                   help="decode through paged KV caches (block-table "
+                        "kernels) instead of dense [B, T] slabs")
+    p.add_argument("--page-size", type=int, default=16,
+                   help="tokens per page with --paged (power of two, "
+                        "16..256)")
     args = p.parse_args()
+    if args.paged and args.graph:
+        print("--paged has no hipGraph loop", file=sys.stderr)
+        return 1
 
-    from torchx_amd.models.generate import KVCache, prefill
+    from torchx_amd.models.generate import KVCache, PagedKVCache, prefill
     from torchx_amd.models.generate import decode_step as decode_step_dense
     from torchx_amd.models.llama import LlamaModel, llama3_8b, llama_gpu_tiny
 
@@ -55,8 +64,26 @@ def main():
         decode_step = decode_step_dense
     B, S0, N = args.batch, args.prompt, args.new
     tokens = torch.randint(0, cfg.vocab_size, (B, S0), device=dev)
-    caches = [KVCache.empty(cfg, B, S0 + N + 8, dev)
-              for _ in range(cfg.num_layers)]
+    if args.paged:
+        # every sequence gets M pages; the table is a seeded permutation
+        # of the physical pages so they are not accidentally contiguous
+        P = args.page_size
+        M = -(-(S0 + N + 8) // P)
+        g = torch.Generator().manual_seed(0)
+        table = (torch.randperm(B * M, generator=g) + 1).to(torch.int32)
+        table = table.reshape(B, M).to(dev)
+        caches = [PagedKVCache.empty(cfg, B * M + 1, P, table, dev)
+                  for _ in range(cfg.num_layers)]
+        pos = torch.full((B,), S0, dtype=torch.int32, device=dev)
+        dense_step = decode_step
+
+        def decode_step(model, tok, caches):  # noqa: F811
+            logits = dense_step(model, tok, caches, pos_dev=pos)
+            pos.add_(1)
+            return logits
+    else:
+        caches = [KVCache.empty(cfg, B, S0 + N + 8, dev)
+                  for _ in range(cfg.num_layers)]
 
     # warm prefill once (hipBLASLt algo selection etc.), then re-time it
     # on fresh caches so the printed number is the steady-state rate
@@ -102,6 +129,8 @@ def main():
         "prefill_tokens_per_second": B * S0 / t_prefill,
         "batch": B, "prompt": S0, "new_tokens": steps,
         "model": args.model, "dtype": "bf16", "data": "synthetic", "graphed": bool(args.graph),
+        "kv_cache": "paged" if args.paged else "dense",
+        "page_size": args.page_size if args.paged else None,
     }))
     return 0
 

@@ -43,6 +43,95 @@ class KVCache:
         )
 
 
+class OutOfPages(RuntimeError):
+    """The page pool cannot supply the pages a request needs."""
+
+
+class PageAllocator:
+    """Host-side free list over the physical pages of a paged KV pool.
+    Page 0 is reserved as the dump page (inactive batch rows read and
+    write only its slot 0) and is never handed out. The free list is
+    LIFO, so a run is deterministic and a freed page goes straight to the
+    next request."""
+
+    def __init__(self, num_pages: int):
+        assert num_pages >= 2, "need the dump page plus one usable page"
+        self.num_pages = num_pages
+        # popped from the end: page 1 is handed out first
+        self._free = list(range(num_pages - 1, 0, -1))
+        self._is_free = [True] * num_pages
+        self._is_free[0] = False
+
+    @property
+    def num_free(self) -> int:
+        return len(self._free)
+
+    def alloc(self, n: int) -> list:
+        """``n`` pages, all or nothing."""
+        if n > len(self._free):
+            raise OutOfPages(f"need {n} pages, {len(self._free)} free")
+        pages = [self._free.pop() for _ in range(n)]
+        for p in pages:
+            self._is_free[p] = False
+        return pages
+
+    def free(self, pages) -> None:
+        for p in pages:
+            assert p != 0, "page 0 is the dump page"
+            assert 0 < p < self.num_pages, f"no such page {p}"
+            assert not self._is_free[p], f"double free of page {p}"
+            self._is_free[p] = True
+            self._free.append(p)
+
+
+@dataclass
+class PagedKVCache:
+    """One layer's paged KV pool. ``block_table`` (int32 [B, M]) is shared
+    by every layer: logical page j of sequence b lives in physical page
+    ``block_table[b, j]`` of each layer's pool. ``row`` narrows the cache
+    to one batch row for a [1, S] prefill (see ``for_row``)."""
+    kpool: torch.Tensor  # [num_pages, P, Hkv, D] bf16
+    vpool: torch.Tensor
+    block_table: torch.Tensor
+    row: Optional[int] = None
+
+    @staticmethod
+    def empty(cfg: LlamaConfig, num_pages: int, page_size: int,
+              block_table: torch.Tensor,
+              device: torch.device) -> "PagedKVCache":
+        assert 16 <= page_size <= 256 and page_size & (page_size - 1) == 0
+        shape = (num_pages, page_size, cfg.num_kv_heads, cfg.head_dim)
+        return PagedKVCache(
+            kpool=torch.zeros(shape, dtype=torch.bfloat16, device=device),
+            vpool=torch.zeros(shape, dtype=torch.bfloat16, device=device),
+            block_table=block_table,
+        )
+
+    @property
+    def page_size(self) -> int:
+        return self.kpool.shape[1]
+
+    def for_row(self, row: int) -> "PagedKVCache":
+        return PagedKVCache(self.kpool, self.vpool, self.block_table, row)
+
+    def store_prefix(self, k: torch.Tensor, v: torch.Tensor) -> None:
+        """Scatter a prefilled prefix into the pages of its row(s):
+        k, v [1, S, Hkv, D] go to row ``self.row``; without a row,
+        [B, S, Hkv, D] go to rows 0..B-1. Plain torch plumbing (one
+        index_copy_ per pool), no host sync."""
+        P = self.page_size
+        B, S = k.shape[:2]
+        r0 = 0 if self.row is None else self.row
+        assert self.row is None or B == 1
+        t = torch.arange(S, device=self.block_table.device)
+        table = self.block_table[r0:r0 + B]
+        slots = (table[:, t // P].long() * P + t % P).reshape(-1)
+        kflat = self.kpool.view(-1, *self.kpool.shape[2:])
+        vflat = self.vpool.view(-1, *self.vpool.shape[2:])
+        kflat.index_copy_(0, slots, k.reshape(B * S, *k.shape[2:]))
+        vflat.index_copy_(0, slots, v.reshape(B * S, *v.shape[2:]))
+
+
 def _split_qkv(qkv: torch.Tensor, cfg: LlamaConfig):
     B, S, _ = qkv.shape
     q, k, v = qkv.split([cfg.q_dim, cfg.kv_dim, cfg.kv_dim], dim=-1)
@@ -66,9 +155,12 @@ def prefill(model: LlamaModel, tokens: torch.Tensor,
         q, k, v = _split_qkv(blk.wqkv(xn), cfg)
         q = ops.rope(q, cos, sin)
         k = ops.rope(k, cos, sin)
-        cache.k[:, :S] = k
-        cache.v[:, :S] = v
-        cache.length = S
+        if isinstance(cache, PagedKVCache):
+            cache.store_prefix(k, v)
+        else:
+            cache.k[:, :S] = k
+            cache.v[:, :S] = v
+            cache.length = S
         attn = ops.flash_attention(q, k, v, causal=True)
         x = x + blk.wo(attn.reshape(B, S, cfg.q_dim))
         xn = ops.rmsnorm(x, blk.mlp_norm, cfg.rms_eps)
@@ -87,24 +179,39 @@ def decode_step(model: LlamaModel, token: torch.Tensor, caches: list,
     scalar) the step is hipGraph-capturable: the cache position comes off
     the device and no host state is read; an int32 [B] ``pos_dev`` runs
     the step RAGGED — every sequence at its own cache position
-    (continuous batching, see ContinuousBatcher)."""
+    (continuous batching, see ContinuousBatcher). ``PagedKVCache``
+    caches take the same [B] vector and go through the block-table
+    kernels (see PagedBatcher)."""
     cfg = model.cfg
     B = token.shape[0]
     blocks = model.blocks
-    pos = caches[0].length if pos_dev is None else pos_dev
+    paged = isinstance(caches[0], PagedKVCache)
+    if paged:
+        assert pos_dev is not None and pos_dev.numel() == B, \
+            "paged caches need an int32 [B] pos_dev"
+        pos = pos_dev
+    else:
+        pos = caches[0].length if pos_dev is None else pos_dev
     x = model.embed(token).reshape(B, -1)  # [B, H] residual stream
     _, xn = ops.rmsnorm_res(x, None, blocks[0].attn_norm, cfg.rms_eps)
     for i, (blk, cache) in enumerate(zip(blocks, caches)):
         qkv = ops.decode_linear(xn, blk.wqkv.weight)
-        q = ops.decode_rope_cache(qkv, cache.k, cache.v, model.rope_cos,
-                                  model.rope_sin, pos, cfg.num_heads)
-        if pos_dev is None:
-            cache.length = pos + 1
-            o = ops.decode_attention(q, cache.k, cache.v, pos + 1)
+        if paged:
+            q = ops.paged_decode_rope_cache(
+                qkv, cache.kpool, cache.vpool, cache.block_table,
+                model.rope_cos, model.rope_sin, pos, cfg.num_heads)
+            o = ops.paged_decode_attention(q, cache.kpool, cache.vpool,
+                                           cache.block_table, pos)
         else:
-            # scalar pos_dev: hipGraph loop; [B] pos_dev: ragged decode
-            # (continuous batching) — each row attends its own length
-            o = ops.decode_attention_dev(q, cache.k, cache.v, pos_dev)
+            q = ops.decode_rope_cache(qkv, cache.k, cache.v, model.rope_cos,
+                                      model.rope_sin, pos, cfg.num_heads)
+            if pos_dev is None:
+                cache.length = pos + 1
+                o = ops.decode_attention(q, cache.k, cache.v, pos + 1)
+            else:
+                # scalar pos_dev: hipGraph loop; [B] pos_dev: ragged decode
+                # (continuous batching) — each row attends its own length
+                o = ops.decode_attention_dev(q, cache.k, cache.v, pos_dev)
         a = ops.decode_linear(o.reshape(B, -1), blk.wo.weight)
         x, xn = ops.rmsnorm_res(x, a, blk.mlp_norm, cfg.rms_eps)
         m = ops.decode_linear(ops.decode_linear_swiglu(xn, blk.wgu.weight),
@@ -310,4 +417,121 @@ class ContinuousBatcher:
             self.pos_host[i] = (self.pos_host[i] + 1) % self.max_len
             if self.active[i] and self.pos_host[i] + 1 >= self.max_len:
                 self.active[i] = False  # out of cache: auto-retire
+        return nxt.reshape(-1)
+
+
+class PagedBatcher:
+    """Continuous batching over a PAGED KV pool: same surface as
+    ContinuousBatcher (``free_rows``, ``admit``, ``retire``, ``step``),
+    but cache memory is committed per ``page_size`` tokens actually
+    produced instead of ``max_len`` rows per batch slot. Many short
+    requests and a few long ones share ``num_pages`` physical pages per
+    layer; a retired row's pages go straight to the next request.
+
+    One int32 [max_batch, M] block table (M = ceil(max_len / page_size))
+    is shared by all layers. Physical page 0 is the dump page: a retired
+    row's table entries are all 0 and its position is 0 and does not
+    advance, so inactive rows read and write only slot 0 of page 0 —
+    never pages that may already belong to someone else. When a row
+    needs a page and the pool is empty, the row is dropped and its index
+    appended to ``self.preempted``.
+    """
+
+    def __init__(self, model, max_batch: int, max_len: int, num_pages: int,
+                 page_size: int = 16, prefill_fn=None, decode_fn=None):
+        self.model = model
+        self.cfg = model.cfg
+        self._prefill = prefill_fn or prefill
+        self._decode = decode_fn or decode_step
+        assert max_len <= self.cfg.max_seq_len, "beyond the rope tables"
+        dev = next(model.parameters()).device
+        self.device = dev
+        self.max_len = max_len
+        self.page_size = page_size
+        self.table_width = -(-max_len // page_size)
+        self.block_table = torch.zeros(max_batch, self.table_width,
+                                       dtype=torch.int32, device=dev)
+        self.caches = [PagedKVCache.empty(self.cfg, num_pages, page_size,
+                                          self.block_table, dev)
+                       for _ in range(self.cfg.num_layers)]
+        self.allocator = PageAllocator(num_pages)
+        self.pages = [[] for _ in range(max_batch)]  # pages owned per row
+        self.pos = torch.zeros(max_batch, dtype=torch.int32, device=dev)
+        self.pos_host = [0] * max_batch
+        # 1 for active rows: only those advance (pos.add_(mask))
+        self.mask = torch.zeros(max_batch, dtype=torch.int32, device=dev)
+        self.tok = torch.zeros(max_batch, 1, dtype=torch.long, device=dev)
+        self.active = [False] * max_batch
+        self.preempted = []
+
+    def free_rows(self) -> list:
+        return [i for i, a in enumerate(self.active) if not a]
+
+    def free_pages(self) -> int:
+        return self.allocator.num_free
+
+    @torch.no_grad()
+    def admit(self, row: int, prompt: torch.Tensor) -> torch.Tensor:
+        """Prefill ``prompt`` [S0] into freshly allocated pages of batch
+        row ``row``; returns the first generated token (scalar tensor).
+        Raises OutOfPages, with no state changed, when the pool cannot
+        hold the prompt plus the first decode position."""
+        assert not self.active[row], f"row {row} is occupied"
+        S0 = prompt.numel()
+        assert S0 + 1 < self.max_len
+        P = self.page_size
+        pages = self.allocator.alloc(-(-(S0 + 1) // P))
+        self.pages[row] = pages
+        self.block_table[row, :len(pages)] = torch.tensor(
+            pages, dtype=torch.int32, device=self.device)
+        logits = self._prefill(self.model,
+                               prompt.reshape(1, S0).to(self.device),
+                               [c.for_row(row) for c in self.caches])
+        nxt = logits.argmax(-1)
+        self.tok[row, 0] = nxt[0]
+        self.pos[row] = S0
+        self.mask[row] = 1
+        self.pos_host[row] = S0
+        self.active[row] = True
+        return nxt[0]
+
+    def retire(self, row: int) -> None:
+        """Free the row's pages and park it on the dump page."""
+        self.allocator.free(self.pages[row])
+        self.pages[row] = []
+        self.block_table[row] = 0
+        self.pos[row] = 0
+        self.mask[row] = 0
+        self.pos_host[row] = 0
+        self.active[row] = False
+
+    @torch.no_grad()
+    def step(self) -> torch.Tensor:
+        """One ragged decode step over ALL rows (inactive rows compute
+        garbage on the dump page that callers ignore — the batch shape
+        stays static). Returns the new tokens [max_batch]; rows dropped
+        for lack of pages are listed in ``self.preempted``."""
+        assert any(self.active), "no active sequences"
+        P = self.page_size
+        for i, on in enumerate(self.active):
+            # this step appends at pos_host[i]: the row must own that page
+            if on and self.pos_host[i] // P >= len(self.pages[i]):
+                try:
+                    page = self.allocator.alloc(1)[0]
+                except OutOfPages:
+                    self.retire(i)
+                    self.preempted.append(i)
+                    continue
+                self.block_table[i, len(self.pages[i])] = page
+                self.pages[i].append(page)
+        logits = self._decode(self.model, self.tok, self.caches,
+                              pos_dev=self.pos)
+        nxt = logits.argmax(-1, keepdim=True)
+        self.tok.copy_(nxt)
+        self.pos.add_(self.mask)
+        for i, on in enumerate(self.active):
+            if on:
+                self.pos_host[i] += 1
+                if self.pos_host[i] + 1 >= self.max_len:
+                    self.retire(i)  # out of cache: auto-retire
         return nxt.reshape(-1)

@@ -23,7 +23,7 @@ import torch
 
 from torchx_amd import ops
 
-from .generate import KVCache
+from .generate import KVCache, PagedKVCache
 from .mixtral import MixtralModel, MoELayer
 
 __all__ = ["prefill_moe", "decode_step_moe", "generate_moe", "KVCache"]
@@ -71,9 +71,12 @@ def prefill_moe(model: MixtralModel, tokens: torch.Tensor,
         k = ops.rope(k.reshape(B, S, cfg.num_kv_heads, cfg.head_dim)
                      .contiguous(), cos, sin)
         v = v.reshape(B, S, cfg.num_kv_heads, cfg.head_dim).contiguous()
-        cache.k[:, :S] = k
-        cache.v[:, :S] = v
-        cache.length = S
+        if isinstance(cache, PagedKVCache):
+            cache.store_prefix(k, v)
+        else:
+            cache.k[:, :S] = k
+            cache.v[:, :S] = v
+            cache.length = S
         attn = ops.flash_attention(q, k, v, causal=True)
         x = x + blk.wo(attn.reshape(B, S, cfg.q_dim))
         xn = ops.rmsnorm(x, blk.mlp_norm, cfg.rms_eps)
@@ -89,22 +92,36 @@ def decode_step_moe(model: MixtralModel, token: torch.Tensor, caches: list,
     half = the fused Llama decode kernels; MLP half = active-expert
     GEMV+SwiGLU. An int32 [B] ``pos_dev`` runs the step RAGGED (every
     sequence at its own cache position — continuous batching); the MoE
-    half is position-independent, so it needs no change."""
+    half is position-independent, so it needs no change. ``PagedKVCache``
+    caches go through the block-table kernels, as in decode_step."""
     cfg = model.cfg
     B = token.shape[0]
     blocks = model.blocks
-    pos = caches[0].length if pos_dev is None else pos_dev
+    paged = isinstance(caches[0], PagedKVCache)
+    if paged:
+        assert pos_dev is not None and pos_dev.numel() == B, \
+            "paged caches need an int32 [B] pos_dev"
+        pos = pos_dev
+    else:
+        pos = caches[0].length if pos_dev is None else pos_dev
     x = model.embed(token).reshape(B, -1)
     _, xn = ops.rmsnorm_res(x, None, blocks[0].attn_norm, cfg.rms_eps)
     for i, (blk, cache) in enumerate(zip(blocks, caches)):
         qkv = ops.decode_linear(xn, blk.wqkv.weight)
-        q = ops.decode_rope_cache(qkv, cache.k, cache.v, model.rope_cos,
-                                  model.rope_sin, pos, cfg.num_heads)
-        if pos_dev is None:
-            cache.length = pos + 1
-            o = ops.decode_attention(q, cache.k, cache.v, pos + 1)
+        if paged:
+            q = ops.paged_decode_rope_cache(
+                qkv, cache.kpool, cache.vpool, cache.block_table,
+                model.rope_cos, model.rope_sin, pos, cfg.num_heads)
+            o = ops.paged_decode_attention(q, cache.kpool, cache.vpool,
+                                           cache.block_table, pos)
         else:
-            o = ops.decode_attention_dev(q, cache.k, cache.v, pos_dev)
+            q = ops.decode_rope_cache(qkv, cache.k, cache.v, model.rope_cos,
+                                      model.rope_sin, pos, cfg.num_heads)
+            if pos_dev is None:
+                cache.length = pos + 1
+                o = ops.decode_attention(q, cache.k, cache.v, pos + 1)
+            else:
+                o = ops.decode_attention_dev(q, cache.k, cache.v, pos_dev)
         a = ops.decode_linear(o.reshape(B, -1), blk.wo.weight)
         x, xn = ops.rmsnorm_res(x, a, blk.mlp_norm, cfg.rms_eps)
         m = _moe_mlp_decode(blk.moe, xn)

@@ -590,6 +590,68 @@ def decode_attention_dev(q: torch.Tensor, kcache: torch.Tensor,
     return torch.cat(outs, dim=0)
 
 
+# ---------------------------------------------------------------------------
+# Paged KV cache (serving): block-table counterparts of decode_attention_dev
+# and decode_rope_cache — ops/csrc/paged_attn.hip. kpool/vpool are
+# [num_pages, P, Hkv, D]; block_table int32 [B, M] maps logical page j of
+# sequence b to a physical page; pos int32 [B] as in decode_attention_dev.
+# ---------------------------------------------------------------------------
+
+
+def paged_decode_attention(q: torch.Tensor, kpool: torch.Tensor,
+                           vpool: torch.Tensor, block_table: torch.Tensor,
+                           pos: torch.Tensor,
+                           scale: Optional[float] = None) -> torch.Tensor:
+    """q [B, Hq, D]; each sequence attends over its own ``pos[b] + 1``
+    logical cache rows, row t read from
+    ``pool[block_table[b, t // P], t % P]`` -> o [B, Hq, D]. On the GPU
+    the result is bit-identical to ``decode_attention_dev`` on the same
+    logical cache."""
+    if scale is None:
+        scale = 1.0 / math.sqrt(q.shape[-1])
+    if _on_gpu(q):
+        return hip_ops().paged_decode_attn(q.contiguous(), kpool, vpool,
+                                           block_table, pos.contiguous(),
+                                           scale)
+    outs = []
+    for b in range(q.shape[0]):
+        n = int(pos[b].item()) + 1
+        outs.append(reference.decode_attention(
+            q[b:b + 1], reference.paged_gather(kpool, block_table[b], n),
+            reference.paged_gather(vpool, block_table[b], n), n, scale))
+    return torch.cat(outs, dim=0)
+
+
+def paged_decode_rope_cache(qkv: torch.Tensor, kpool: torch.Tensor,
+                            vpool: torch.Tensor, block_table: torch.Tensor,
+                            cos: torch.Tensor, sin: torch.Tensor,
+                            pos: torch.Tensor,
+                            num_heads: int) -> torch.Tensor:
+    """Fused decode rope + paged cache append: qkv [B, (Hq+2*Hkv)*D] for
+    one position -> roped q [B, Hq, D]; the roped k and raw v of sequence
+    b land in pool slot ``block_table[b, pos[b] // P] * P + pos[b] % P``.
+    cos/sin are the FULL f32 [S, D/2] tables; ``pos`` is int32 [B]."""
+    B = qkv.shape[0]
+    P, Hkv, D = kpool.shape[1], kpool.shape[2], kpool.shape[3]
+    if _on_gpu(qkv):
+        return hip_ops().paged_decode_rope_cache(
+            qkv.contiguous(), kpool, vpool, block_table, cos, sin,
+            pos.contiguous())
+    q, k, v = qkv.split([num_heads * D, Hkv * D, Hkv * D], dim=-1)
+    q = q.reshape(B, 1, num_heads, D)
+    k = k.reshape(B, 1, Hkv, D)
+    v = v.reshape(B, 1, Hkv, D)
+    outs = []
+    for b in range(B):
+        p = int(pos[b].item())
+        page = int(block_table[b, p // P].item())
+        cs, sn = cos[p:p + 1], sin[p:p + 1]
+        outs.append(rope(q[b:b + 1].contiguous(), cs, sn))
+        kpool[page, p % P] = rope(k[b:b + 1].contiguous(), cs, sn)[0, 0]
+        vpool[page, p % P] = v[b, 0]
+    return torch.cat(outs, dim=0).reshape(B, num_heads, D)
+
+
 def decode_linear(x: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
     """Skinny-M linear for the decode path: x [..., M, K] with M <= 8
     total rows -> x @ w.T via the W-stream-bound ``gemv_bf16`` kernel

@@ -55,6 +55,14 @@ void rmsnorm_res_launch(const void*, const void*, const void*, void*, void*,
                         long, int, float, hipStream_t);
 void gemv_swiglu_launch(const void*, const void*, void*, int, int, int,
                         hipStream_t);
+void paged_decode_attn_launch(const void*, const void*, const void*, void*,
+                              void*, void*, const void*, const void*, int,
+                              int, int, int, int, int, int, float,
+                              hipStream_t);
+void paged_decode_rope_cache_launch(const void*, void*, void*, void*,
+                                    const void*, const void*, const void*,
+                                    const void*, int, int, int, int, int,
+                                    int, int, hipStream_t);
 }
 
 namespace {
@@ -524,6 +532,100 @@ at::Tensor decode_rope_cache(at::Tensor qkv, at::Tensor kc, at::Tensor vc,
   return q;
 }
 
+// ---- paged KV cache (block-table) decode -----------------------------------
+// kpool/vpool [num_pages, P, Hkv, 128] bf16; block_table int32 [B, M]
+// (logical page j of sequence b -> physical page); pos int32 [B]. The
+// kernels clamp every table entry and position, so the checks here are
+// about shapes and dtypes only. Returns log2(P).
+int check_paged(const at::Tensor& kpool, const at::Tensor& vpool,
+                const at::Tensor& bt, const at::Tensor& pos, long B) {
+  check_bf16(kpool, "kpool");
+  check_bf16(vpool, "vpool");
+  TORCH_CHECK(kpool.dim() == 4 && kpool.sizes() == vpool.sizes(),
+              "kpool/vpool must be 4-D [num_pages, P, Hkv, 128] with "
+              "identical shapes");
+  TORCH_CHECK(kpool.size(3) == 128, "head_dim must be 128");
+  const long P = kpool.size(1);
+  TORCH_CHECK(P >= 16 && P <= 256 && (P & (P - 1)) == 0,
+              "page size must be a power of two in [16, 256]");
+  TORCH_CHECK(kpool.size(0) >= 1 && kpool.size(0) * P < (1L << 31),
+              "invalid num_pages");
+  TORCH_CHECK(bt.is_cuda() && bt.scalar_type() == at::kInt &&
+                  bt.dim() == 2 && bt.is_contiguous(),
+              "block_table must be a contiguous int32 [B, M] device tensor");
+  TORCH_CHECK(bt.size(0) == B, "block_table rows must equal the batch");
+  TORCH_CHECK(bt.size(1) >= 1 && bt.size(1) * P < (1L << 31),
+              "invalid block_table width");
+  TORCH_CHECK(pos.is_cuda() && pos.scalar_type() == at::kInt &&
+                  pos.is_contiguous() && pos.numel() == B,
+              "pos must be a contiguous int32 [B] device tensor");
+  int logP = 0;
+  while ((1L << logP) < P) ++logP;
+  return logP;
+}
+
+at::Tensor paged_decode_attn(at::Tensor q, at::Tensor kpool,
+                             at::Tensor vpool, at::Tensor bt, at::Tensor pos,
+                             double scale) {
+  check_bf16(q, "q");
+  TORCH_CHECK(q.dim() == 3 && q.size(2) == 128, "q must be [B, Hq, 128]");
+  const int B = q.size(0), Hq = q.size(1);
+  const int logP = check_paged(kpool, vpool, bt, pos, B);
+  const int num_pages = kpool.size(0), Hkv = kpool.size(2);
+  const int M = bt.size(1);
+  TORCH_CHECK(Hq % Hkv == 0, "GQA group mismatch");
+  auto o = at::empty_like(q);
+  const int split = std::max(1, std::min(16, 512 / (B * Hq)));
+  at::Tensor ml, oacc;
+  void* mlp = nullptr;
+  void* oaccp = nullptr;
+  if (split > 1) {
+    ml = at::empty({(long)B * Hq * split * 2},
+                   q.options().dtype(at::kFloat));
+    oacc = at::empty({(long)B * Hq * split * 128},
+                     q.options().dtype(at::kFloat));
+    mlp = ml.data_ptr();
+    oaccp = oacc.data_ptr();
+  }
+  paged_decode_attn_launch(q.data_ptr(), kpool.data_ptr(), vpool.data_ptr(),
+                           mlp, oaccp, o.data_ptr(), bt.data_ptr(),
+                           pos.data_ptr(), B, Hq, Hkv, num_pages, logP, M,
+                           split, (float)scale, cur_stream());
+  return o;
+}
+
+// qkv [B, (Hq+2*Hkv)*128] (one position): ropes q/k at pos[b], appends
+// k/v to the pools at slot bt[b][pos/P]*P + pos%P, returns q [B, Hq, 128].
+at::Tensor paged_decode_rope_cache(at::Tensor qkv, at::Tensor kpool,
+                                   at::Tensor vpool, at::Tensor bt,
+                                   at::Tensor cos_t, at::Tensor sin_t,
+                                   at::Tensor pos) {
+  check_bf16(qkv, "qkv");
+  check_f32(cos_t, "cos");
+  check_f32(sin_t, "sin");
+  TORCH_CHECK(qkv.dim() == 2, "qkv must be [B, (Hq+2*Hkv)*128]");
+  const int B = qkv.size(0);
+  const int logP = check_paged(kpool, vpool, bt, pos, B);
+  const int num_pages = kpool.size(0), Hkv = kpool.size(2);
+  const int M = bt.size(1);
+  TORCH_CHECK(cos_t.dim() == 2 && cos_t.size(1) == 64 &&
+                  cos_t.size(0) >= 1 && sin_t.sizes() == cos_t.sizes(),
+              "cos/sin must be [S, 64] (head_dim 128)");
+  const long nh = qkv.size(1) / 128;
+  const int Hq = (int)nh - 2 * Hkv;
+  TORCH_CHECK(Hq >= 1 && qkv.size(1) == nh * 128, "qkv width mismatch");
+  TORCH_CHECK(Hq % Hkv == 0, "GQA group mismatch");
+  const int rope_rows = (int)std::min<long>(cos_t.size(0), 1L << 30);
+  auto q = at::empty({B, (long)Hq, 128}, qkv.options());
+  paged_decode_rope_cache_launch(qkv.data_ptr(), q.data_ptr(),
+                                 kpool.data_ptr(), vpool.data_ptr(),
+                                 bt.data_ptr(), cos_t.data_ptr(),
+                                 sin_t.data_ptr(), pos.data_ptr(), B, Hq,
+                                 Hkv, num_pages, logP, M, rope_rows,
+                                 cur_stream());
+  return q;
+}
+
 // ---- fused residual add + rmsnorm (inference) ------------------------------
 // s = x + res, y = rmsnorm(s) * w; returns (s, y). res omitted -> plain
 // rmsnorm (s aliases x).
@@ -604,6 +706,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("qkv"), py::arg("kc"), py::arg("vc"), py::arg("cos"),
         py::arg("sin"), py::arg("pos") = 0,
         py::arg("pos_dev") = c10::nullopt);
+  m.def("paged_decode_attn", &paged_decode_attn);
+  m.def("paged_decode_rope_cache", &paged_decode_rope_cache);
   m.def("rmsnorm_res", &rmsnorm_res,
         py::arg("x"), py::arg("res"), py::arg("w"), py::arg("eps"));
 }

@@ -117,3 +117,15 @@ def decode_attention(q: torch.Tensor, kcache: torch.Tensor,
     s = torch.einsum("bhd,blhd->bhl", q.float(), k) * scale
     p = torch.softmax(s, dim=-1)
     return torch.einsum("bhl,blhd->bhd", p, v).to(q.dtype)
+
+
+def paged_gather(pool: torch.Tensor, table_row: torch.Tensor,
+                 length: int) -> torch.Tensor:
+    """Logical view of one sequence of a paged KV pool: ``pool``
+    [num_pages, P, Hkv, D], ``table_row`` int [M] (logical page j lives in
+    physical page ``table_row[j]``) -> the first ``length`` logical rows,
+    [1, length, Hkv, D]."""
+    P = pool.shape[1]
+    n = (length + P - 1) // P
+    pages = table_row[:n].long()
+    return pool[pages].reshape(1, n * P, *pool.shape[2:])[:, :length]
