@@ -43,8 +43,15 @@ def main():
                    choices=["stream", "recompute"],
                    help="dQ path of the backward (default: the extension's "
                         "own default, see ops.set_attn_bwd_dq_mode)")
+    p.add_argument("--dkv-impl", type=str, default=None,
+                   choices=["merged", "split"],
+                   help="dK/dV kernel of the backward (default: the "
+                        "extension's own default, see "
+                        "ops.set_attn_bwd_dkv_impl)")
     args = p.parse_args()
     B, S, Hq, Hkv, D = args.B, args.S, args.Hq, args.Hkv, 128
+    if args.dkv_impl is not None:
+        ops.set_attn_bwd_dkv_impl(args.dkv_impl)
     if args.dq_mode is not None:
         ops.set_attn_bwd_dq_mode(args.dq_mode)
 

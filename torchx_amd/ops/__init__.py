@@ -310,6 +310,18 @@ def get_attn_bwd_dq_mode() -> str:
     return hip_ops().get_attn_bwd_dq_mode()
 
 
+def set_attn_bwd_dkv_impl(impl: str) -> None:
+    """Select the dK/dV kernel of the attention backward: "merged" (default;
+    one wave per SIMD accumulates both outputs, so S, P and dP are computed
+    once) or "split" (separate dV and dK waves).  Both produce the same
+    bits.  The initial value comes from TORCHX_AMD_DKV_IMPL."""
+    hip_ops().set_attn_bwd_dkv_impl(impl)
+
+
+def get_attn_bwd_dkv_impl() -> str:
+    return hip_ops().get_attn_bwd_dkv_impl()
+
+
 def flash_attention(
     q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
     causal: bool = True, scale: Optional[float] = None,

@@ -26,11 +26,13 @@
 //    or above (staging amortizes over 2x compute once causal wave-skew
 //    is relatively small).
 //  * Backward is FA2-style without atomics: preprocess delta =
-//    rowsum(dO*O); ONE combined 8-wave dK+dV kernel where waves w and
-//    w+4 own the same 32 kv rows (dV / dK roles) so Q/dO are staged once
-//    for both outputs, and whose dK waves export the scaled bf16 dS; a dQ
-//    kernel (grid over q tiles) that is a streamed GEMM dS.K over that
-//    export (the dQ kernel that recomputes dS itself remains selectable).
+//    rowsum(dO*O); ONE dK+dV kernel, 4 waves at one wave per SIMD, in
+//    which a wave accumulates both dK and dV for its 32 kv rows (S, P and
+//    dP computed once) and exports the scaled bf16 dS (the 8-wave kernel
+//    with separate dV / dK waves, which computes the same bits, remains
+//    selectable); a dQ kernel (grid over q tiles) that is a streamed GEMM
+//    dS.K over that export (the dQ kernel that recomputes dS itself
+//    remains selectable).
 //
 // MFMA fragment maps used (verified against rocm CK xdlops_gemm.hpp and the
 // CDNA4 guide; C/D map from the guide):
@@ -38,6 +40,10 @@
 //   B[k=16, n=32]: lane l holds B[(l>>5)*8 + j][l&31]
 //   C[m=32, n=32]: lane l holds C[(r&3) + 8*(r>>2) + 4*(l>>5)][l&31], r=0..15
 #include "common.h"
+
+#include <cstdlib>
+#include <cstring>
+#include <type_traits>
 
 typedef __bf16 mbf16x8 __attribute__((ext_vector_type(8)));
 
@@ -1205,6 +1211,484 @@ attn_bwd_dkv_kernel(const unsigned short* __restrict__ q,
   }
 }
 
+// cvals_to_frags over already packed bf16 pairs, with the lane-half
+// exchange done by v_permlane32_swap (gfx950): swap(a, b) trades a's upper
+// 32 lanes for b's lower 32, so (a01, a45) -> (w0, w2) and (a23, a67) ->
+// (w1, w3) in one VALU op each — the same words the shfl_xor + select form
+// builds, without its eight trips through the LDS pipe.
+__device__ __forceinline__ void packed_to_frags_swap(const unsigned int* a,
+                                                     mbf16x8* f0,
+                                                     mbf16x8* f1) {
+  // a[4 * s + i] = pack(p[8 * s + 2 * i], p[8 * s + 2 * i + 1])
+  unsigned int w[2][4];
+  #pragma unroll
+  for (int s = 0; s < 2; ++s) {
+    auto e0 = __builtin_amdgcn_permlane32_swap(a[4 * s + 0], a[4 * s + 2],
+                                               false, false);
+    auto e1 = __builtin_amdgcn_permlane32_swap(a[4 * s + 1], a[4 * s + 3],
+                                               false, false);
+    w[s][0] = e0[0];
+    w[s][1] = e1[0];
+    w[s][2] = e0[1];
+    w[s][3] = e1[1];
+  }
+  uint4_v u0 = {w[0][0], w[0][1], w[0][2], w[0][3]};
+  uint4_v u1 = {w[1][0], w[1][1], w[1][2], w[1][3]};
+  *f0 = __builtin_bit_cast(mbf16x8, u0);
+  *f1 = __builtin_bit_cast(mbf16x8, u1);
+}
+
+// ---------------------------------------------------------------------------
+// Backward dK+dV, merged roles: one 4-wave kernel at ONE wave per SIMD (the
+// 512-register budget of gfx950: 256 VGPR + 256 AGPR).  Wave w owns kv rows
+// [kt*128 + 32w, +32) and accumulates BOTH dV and dK, so S^T, P and dP are
+// computed once per sub-tile (32 MFMAs where the split kernel's wave pair
+// issues 40; one mask/exp2 pass instead of two; 16 Q/dO fragment reads
+// instead of 24).  Every expression, and the order of every accumulation,
+// is the split kernel's, so dk, dv and the exported dS are bit-identical.
+//
+// At one wave per SIMD nothing hides a latency for free, so the tile body
+// is a hand-staged software pipeline over pairs of 32-q sub-tiles: LDS
+// reads are issued in groups ahead of their MFMAs, and the S/dP chain of
+// the second sub-tile runs chunk by chunk under the mask/exp2 VALU of the
+// first (see the stage list in the loop).  The block mapping, the staged
+// images, the lse/delta double buffer, the dS image layout and the
+// epilogue are the split kernel's.  The next tile's lse/delta value is
+// loaded into one register at the loop head, next to the glds issue, and
+// written to LDS at the tile end.
+// ---------------------------------------------------------------------------
+template <int TFKV>
+__global__ void __launch_bounds__(256, 1)
+attn_bwd_dkv_merged_kernel(const unsigned short* __restrict__ q,
+                           const unsigned short* __restrict__ k,
+                           const unsigned short* __restrict__ v,
+                           const unsigned short* __restrict__ dout,
+                           const float* __restrict__ lse,
+                           const float* __restrict__ delta,
+                           unsigned short* __restrict__ dk,
+                           unsigned short* __restrict__ dv,
+                           char* __restrict__ ds,  // dS scratch, or null
+                           int B, int S, int Hq, int Hkv, float scale,
+                           int causal, long q_rs, long kv_rs, long dout_rs,
+                           long out_rs) {
+  constexpr int NS = TFKV / 32;  // 32-q sub-tiles per staged tile
+  __shared__ __align__(16) char smem[4 * (TFKV * 256)];
+  __shared__ __align__(16) float lse_buf[2][TFKV], del_buf[2][TFKV];
+  char* qn_c = smem;                       // Q natural cur
+  char* don_c = smem + TFKV * 256;         // dO natural cur
+  char* qn_n = smem + 2 * (TFKV * 256);
+  char* don_n = smem + 3 * (TFKV * 256);
+
+  const int nkt = (S + BLOCK_K - 1) / BLOCK_K;
+  const int G = Hq / Hkv;
+  int b, hkv, kt;
+  {
+    int bid = blockIdx.x;
+    if (((B * Hkv) & 7) == 0) {
+      const int xcd = bid & 7, slot = bid >> 3;
+      const int g = (slot / nkt) * 8 + xcd;
+      b = g / Hkv;
+      hkv = g % Hkv;
+      kt = slot % nkt;
+    } else {
+      b = bid / (Hkv * nkt);
+      bid -= b * Hkv * nkt;
+      hkv = bid / nkt;
+      kt = bid % nkt;
+    }
+  }
+
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / 64);
+  const int lane = threadIdx.x & 63;
+  const bool hi = lane >= 32;
+  const int kr = lane & 31;
+
+  const long q_seq_stride = q_rs;
+  const long kv_seq_stride = kv_rs;
+  const unsigned short* kb = k + (long)b * S * kv_seq_stride + (long)hkv * HD;
+  const unsigned short* vb = v + (long)b * S * kv_seq_stride + (long)hkv * HD;
+
+  const int kv0_blk = kt * BLOCK_K;
+  const int kw0 = kv0_blk + wave * KBLK;  // this wave's 32 kv rows
+  const long k_row = kw0 + kr;
+  const bool wave_active = kw0 < S;
+  const bool krow_valid = k_row < S;
+
+  // K and V rows of this wave stay resident
+  mbf16x8 kfrag[8], vfrag[8];
+  {
+    const long row = krow_valid ? k_row : (S - 1);
+    const unsigned short* kp = kb + row * kv_seq_stride + (hi ? 8 : 0);
+    const unsigned short* vp = vb + row * kv_seq_stride + (hi ? 8 : 0);
+    #pragma unroll
+    for (int c = 0; c < 8; ++c) {
+      kfrag[c] = __builtin_bit_cast(mbf16x8, *(const ushort8*)(kp + c * 16));
+      vfrag[c] = __builtin_bit_cast(mbf16x8, *(const ushort8*)(vp + c * 16));
+    }
+  }
+
+  f32x16 accv[4] = {}, acck[4] = {};
+  const float sc2 = scale * LOG2E;
+
+  const int t0 = causal ? (kv0_blk / TFKV) : 0;
+  const int nt = (S + TFKV - 1) / TFKV;
+  const int nt_eff = nt - t0;
+  const int total = G * nt_eff;
+
+  // dS export: this lane's 16 B slot inside an image — k row kr, q octet
+  // hi (f0) / 2 + hi (f1) — plus the wave's k sub-tile
+  const bool ds_on = ds != nullptr;
+  const int ds_nqt = (S + BLOCK_Q - 1) / BLOCK_Q;
+  const long ds_plane = ds_qt_base(ds_nqt, ds_nqt, causal);
+  const long ds_lane = (long)(kw0 / KBLK) * (4 * DS_IMG_BYTES) + kr * 64 +
+                       (hi ? 16 : 0);
+
+  auto head_q = [&](int gh) {
+    return q + (long)b * S * q_seq_stride + (long)(hkv * G + gh) * HD;
+  };
+  auto head_do = [&](int gh) {
+    return dout + (long)b * S * dout_rs + (long)(hkv * G + gh) * HD;
+  };
+  // lse (threads [0, TFKV)) / delta (threads [TFKV, 2*TFKV)) value of tile
+  // (gh, t) for this thread, and its slot in the LDS buffers
+  auto load_lse = [&](int gh, int t) -> float {
+    const int hq_ = hkv * G + gh;
+    const int q0_ = t * TFKV;
+    float x = 0.f;
+    if (threadIdx.x < TFKV) {
+      const float* lse_b = lse + ((long)b * Hq + hq_) * S;
+      const int qg = q0_ + threadIdx.x;
+      x = (qg < S) ? lse_b[qg] : 0.f;
+    } else if (threadIdx.x < 2 * TFKV) {
+      const float* del_b = delta + ((long)b * Hq + hq_) * S;
+      const int qg = q0_ + (threadIdx.x - TFKV);
+      x = (qg < S) ? del_b[qg] : 0.f;
+    }
+    return x;
+  };
+  // (the lse value is scaled here, not at the load: an ALU use of the
+  // loaded register at the loop head would wait for the load and, with
+  // it, for every glds piece issued in front of it)
+  auto store_lse = [&](int buf, float x) {
+    if (threadIdx.x < TFKV) {
+      lse_buf[buf][threadIdx.x] = x * LOG2E;
+    } else if (threadIdx.x < 2 * TFKV) {
+      del_buf[buf][threadIdx.x - TFKV] = x;
+    }
+  };
+
+  // prologue: tile (gh=0, t=t0) — glds the natural images
+  stage_k_glds<4, TFKV>(head_q(0), (long)t0 * TFKV, q_seq_stride, S, qn_c);
+  stage_k_glds<4, TFKV>(head_do(0), (long)t0 * TFKV, dout_rs, S, don_c);
+  asm volatile("s_waitcnt vmcnt(0)");
+  store_lse(0, load_lse(0, t0));
+  __syncthreads();
+
+  const float* lse_cur = lse_buf[0];
+  const float* del_cur = del_buf[0];
+  int lse_nxt = 1;
+  for (int idx = 0; idx < total; ++idx) {
+    const int gh = idx / nt_eff;
+    const int t = t0 + idx % nt_eff;
+    const int q0 = t * TFKV;
+    const int hq = hkv * G + gh;
+    const bool has_next = (idx + 1) < total;
+    const int ngh = (idx + 1) / nt_eff;
+    const int ntile = t0 + (idx + 1) % nt_eff;
+    float lse_reg = 0.f;
+    if (has_next) {
+      // async glds issue BEFORE compute: their latency hides under the
+      // S/dP chain and the softmax of the first sub-tile.  The next
+      // tile's lse/delta value rides along in ONE register, so the
+      // barrier at the tile end does not wait on a fresh global load.
+      stage_k_glds<4, TFKV>(head_q(ngh), (long)ntile * TFKV, q_seq_stride, S,
+                            qn_n);
+      stage_k_glds<4, TFKV>(head_do(ngh), (long)ntile * TFKV, dout_rs, S,
+                            don_n);
+      lse_reg = load_lse(ngh, ntile);
+    }
+
+    // first sub-tile of this tile that is not fully masked for the wave's
+    // kv rows (uniform); NS when the wave has nothing to do in the tile
+    int sb0 = 0;
+    if (causal && kw0 > q0) sb0 = (kw0 - q0) / 32;
+    if (!wave_active || sb0 > NS) sb0 = NS;
+    sb0 = __builtin_amdgcn_readfirstlane(sb0);
+
+    int n_ds = 0;   // dS stores issued behind this tile's glds pieces
+    char* ds_head = ds + ((long)b * Hq + hq) * ds_plane * (4 * DS_IMG_BYTES)
+                    + ds_lane;
+
+    // The tile body is written as explicit stages so that LDS reads are
+    // issued in groups AHEAD of the MFMAs that consume them (at one wave
+    // per SIMD nothing else hides an LDS round trip; the compiler's own
+    // order was read -> lgkmcnt(0) -> MFMA, one at a time):
+    //   A  the first Q/dO fragment reads of sub-tile sb+1
+    //   B  S/dP chain of sb+1 (MFMA) interleaved with the mask/exp2 pass
+    //      of sb (VALU), plus the remaining fragment reads and the
+    //      transpose reads of sb for dt 0,1
+    //   C  accumulate MFMAs of sb; the dS export behind the first group;
+    //      the transpose reads for dt 2,3 fly under the dt 0,1 MFMAs
+    auto load_frags = [&](int sb, mbf16x8* qf, mbf16x8* of) {
+      #pragma unroll
+      for (int c = 0; c < 8; ++c) {
+        qf[c] = kimg_frag(qn_c, sb, c);
+        of[c] = kimg_frag(don_c, sb, c);
+      }
+    };
+    // S[q, k own] and dP[q, k own] (lane owns the k column; q rows via
+    // c_row so the contraction dim of the accumulate MFMAs is the C-row
+    // dim)
+    auto s_chain = [&](const mbf16x8* qf, const mbf16x8* of, f32x16& s_out,
+                       f32x16& dp_out) {
+      f32x16 s = {}, dp = {};
+      #pragma unroll
+      for (int c = 0; c < 8; ++c) {
+        s = mfma32(qf[c], kfrag[c], s);
+        dp = mfma32(of[c], vfrag[c], dp);
+      }
+      s_out = s;
+      dp_out = dp;
+    };
+
+    if (sb0 < NS) {
+      // In the diagonal tile of a causal head the sub-tiles in front of
+      // sb0 are fully masked for this wave; they run all the same (p and
+      // dS come out as exact zeros, which leave the accumulators as they
+      // are) and only their export is skipped: the tile ends at a barrier
+      // behind wave 0, whose sb0 is 0 there, so skipping them would not
+      // end it sooner, and a second entry into the pipelined body costs
+      // the compiler its register allocation.
+      // The pipeline runs over PAIRS of sub-tiles (64 q rows): a rolled
+      // loop over the pairs of a 128-row tile, whose second chain start is
+      // not overlapped — four sub-tiles in one straight line cost more
+      // registers than the wave has.
+      #pragma clang loop unroll(disable)
+      for (int sbase = 0; sbase < NS; sbase += 2) {
+        f32x16 acc_s[2], acc_dp[2];
+        mbf16x8 qf[8], of[8];
+        load_frags(sbase, qf, of);
+        __builtin_amdgcn_sched_barrier(0);
+        s_chain(qf, of, acc_s[0], acc_dp[0]);
+        #pragma unroll
+        for (int u = 0; u < 2; ++u) {
+          const int sb = sbase + u;
+          const bool nx = u == 0;
+          const f32x16& cs = acc_s[u];
+          const f32x16& cdp = acc_dp[u];
+          // stage A: the first half of the next chain's fragments and this
+          // sub-tile's first lse/delta values (C-layout rows 8j + 4*hi +
+          // 0..3 are 16 B runs); the rest is read inside stage B, eight
+          // chunks (fragments) or four (lse/delta) ahead of its use, so
+          // that only a window of them is live
+          if (nx) {
+            #pragma unroll
+            for (int c = 0; c < 4; ++c) {
+              qf[c] = kimg_frag(qn_c, sb + 1, c);
+              of[c] = kimg_frag(don_c, sb + 1, c);
+            }
+          }
+          f32x4 lv[4], dl[4];
+          lv[0] = *(const f32x4*)(lse_cur + 32 * sb + (hi ? 4 : 0));
+          dl[0] = *(const f32x4*)(del_cur + 32 * sb + (hi ? 4 : 0));
+          __builtin_amdgcn_sched_barrier(0);
+
+          // stage B, in 16 chunks pinned by sched_barriers: one MFMA of the
+          // next chain, then the mask/exp2 VALU of one C-value, which runs
+          // while the matrix pipe works; the transpose reads for dt 0,1
+          // ride in the second half (in the first sub-tile of a tile the
+          // compiler puts a vmcnt(0) in front of them for the glds pieces
+          // in flight, so they must not come early)
+          const int qs0 = q0 + 32 * sb;
+          // causal masking only bites when SOME (q, k) pair in this
+          // 32q x 32k(own) tile has k > q, i.e. qs0 < kw0 + 32
+          const bool mask_tile = (causal && qs0 < kw0 + 32)
+                                 || (qs0 + 32 > S) || !krow_valid;
+          mbf16x8 p0, p1, d0, d1;
+          mbf16x8 tv[8], tk[8];   // [2 * dt + k-slice]
+          auto stage_b = [&](auto masked) {
+            float cp[16], cd[16];
+            unsigned int pp[8], pd[8];   // packed bf16 pairs of cp / cd
+            f32x16 ns = {}, ndp = {};
+            #pragma unroll
+            for (int r = 0; r < 16; ++r) {
+              if (nx) {
+                if (r & 1) {
+                  ndp = mfma32(of[r >> 1], vfrag[r >> 1], ndp);
+                } else {
+                  ns = mfma32(qf[r >> 1], kfrag[r >> 1], ns);
+                }
+                if (r < 8 && !(r & 1)) {
+                  qf[4 + (r >> 1)] = kimg_frag(qn_c, sb + 1, 4 + (r >> 1));
+                  of[4 + (r >> 1)] = kimg_frag(don_c, sb + 1, 4 + (r >> 1));
+                }
+              }
+              if (r < 12 && !(r & 3)) {
+                const int j = (r >> 2) + 1;
+                lv[j] = *(const f32x4*)(lse_cur + 32 * sb + 8 * j +
+                                        (hi ? 4 : 0));
+                dl[j] = *(const f32x4*)(del_cur + 32 * sb + 8 * j +
+                                        (hi ? 4 : 0));
+              }
+              if (r >= 8) {
+                const int i = r - 8, dt = i >> 2;
+                if (i & 2) {
+                  tk[2 * dt + (i & 1)] =
+                      nat_tr_frag(qn_c, 2 * sb + (i & 1), dt);
+                } else {
+                  tv[2 * dt + (i & 1)] =
+                      nat_tr_frag(don_c, 2 * sb + (i & 1), dt);
+                }
+              }
+              {
+                // the split kernel rounds s*sc2 before it subtracts lse (its
+                // mask select sits between the two): no fused multiply-add
+                // here either, or dS and P differ in the last bit
+                #pragma clang fp contract(off)
+                const int ql = 32 * sb + c_row(r, hi);  // q offset in tile
+                float s2 = cs[r] * sc2;
+                if (decltype(masked)::value) {
+                  const long qg = q0 + ql;
+                  if (qg >= S || !krow_valid || (causal && k_row > qg)) {
+                    s2 = -3.0e38f;
+                  }
+                }
+                const float pr =
+                    __builtin_amdgcn_exp2f(s2 - lv[r >> 2][r & 3]);
+                cp[r] = pr;
+                cd[r] = scale * pr * (cdp[r] - dl[r >> 2][r & 3]);
+              }
+              if (r & 1) {
+                pp[r >> 1] = pack_bf16x2(cp[r - 1], cp[r]);
+                pd[r >> 1] = pack_bf16x2(cd[r - 1], cd[r]);
+              }
+              __builtin_amdgcn_sched_barrier(0);
+            }
+            if (nx) {
+              acc_s[1] = ns;
+              acc_dp[1] = ndp;
+            }
+            packed_to_frags_swap(pp, &p0, &p1);
+            packed_to_frags_swap(pd, &d0, &d1);
+          };
+          // the mask_tile gate is a uniform branch around the WHOLE stage,
+          // so the MFMAs and the VALU stay in one block either way
+          if (mask_tile) {
+            stage_b(std::true_type{});
+          } else {
+            stage_b(std::false_type{});
+          }
+          __builtin_amdgcn_sched_barrier(0);
+
+          // stage C: dV[k,d] += P^T . dO ; dK[k,d] += dS^T . Q — B fragments
+          // by hardware transpose read from the natural images (T10)
+          accv[0] = mfma32(p0, tv[0], accv[0]);
+          accv[0] = mfma32(p1, tv[1], accv[0]);
+          acck[0] = mfma32(d0, tk[0], acck[0]);
+          acck[0] = mfma32(d1, tk[1], acck[0]);
+          // the transpose reads for dt 2,3 go out first, under the MFMAs
+          // just issued (behind the export they would wait for its stores:
+          // the compiler drains vmcnt in front of them)
+          __builtin_amdgcn_sched_barrier(0);
+          #pragma unroll
+          for (int dt = 2; dt < 4; ++dt) {
+            tv[2 * dt] = nat_tr_frag(don_c, 2 * sb, dt);
+            tv[2 * dt + 1] = nat_tr_frag(don_c, 2 * sb + 1, dt);
+            tk[2 * dt] = nat_tr_frag(qn_c, 2 * sb, dt);
+            tk[2 * dt + 1] = nat_tr_frag(qn_c, 2 * sb + 1, dt);
+          }
+          // export the scaled dS^T sub-tile whole (masked elements are exact
+          // zeros; sub-tiles that start past the last q row are not stored):
+          // 2 x 16 B per lane, 2 KiB contiguous per wave, behind the first
+          // accumulate group and the vmcnt(0) the compiler puts in front of
+          // the first transpose read while glds pieces are in flight
+          __builtin_amdgcn_sched_barrier(0);
+          if (ds_on && sb >= sb0 && qs0 < S) {
+            char* p = ds_head +
+                      (ds_qt_base(qs0 / BLOCK_Q, ds_nqt, causal) * 4 +
+                       ((qs0 / QBLK) & 3)) * DS_IMG_BYTES;
+            *(uint4_v*)p = __builtin_bit_cast(uint4_v, d0);
+            *(uint4_v*)(p + 32) = __builtin_bit_cast(uint4_v, d1);
+            n_ds = 2;
+          }
+          __builtin_amdgcn_sched_barrier(0);
+          #pragma unroll
+          for (int dt = 1; dt < 4; ++dt) {
+            accv[dt] = mfma32(p0, tv[2 * dt], accv[dt]);
+            accv[dt] = mfma32(p1, tv[2 * dt + 1], accv[dt]);
+            acck[dt] = mfma32(d0, tk[2 * dt], acck[dt]);
+            acck[dt] = mfma32(d1, tk[2 * dt + 1], acck[dt]);
+          }
+        }
+      }
+    }
+
+    if (has_next) {
+      // own glds of the nxt tiles (and the lse/delta register) done.
+      // vmcnt counts stores too, in issue order: when this tile exported,
+      // its last two stores are younger than every load, so the wait may
+      // leave those two in flight
+      if (n_ds) {
+        asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
+      } else {
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      }
+      // (the compiler still guards lse_reg with a vmcnt(0) of its own in
+      // front of this write — it cannot count the conditional stores —
+      // so for now the two stores are drained here after all; they have
+      // had the 12 MFMAs behind the export to complete)
+      store_lse(lse_nxt, lse_reg);
+      // ONE barrier per tile publishes everything: a bare s_barrier
+      // behind lgkmcnt(0) (the lse/delta write above), without the fence
+      // of a __syncthreads, which drains vmcnt to 0 by itself
+      asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+      lse_cur = lse_buf[lse_nxt];
+      del_cur = del_buf[lse_nxt];
+      lse_nxt ^= 1;
+      char* tp;
+      tp = qn_c; qn_c = qn_n; qn_n = tp;
+      tp = don_c; don_c = don_n; don_n = tp;
+    }
+  }
+
+  // store via LDS transpose (8-B global writes); wave-private f32 region,
+  // once per output
+  __syncthreads();
+  float* tr = (float*)smem + wave * (32 * 36);
+  if (wave_active) {
+    #pragma unroll
+    for (int o = 0; o < 2; ++o) {
+      unsigned short* out = o ? dk : dv;
+      #pragma unroll
+      for (int dt = 0; dt < 4; ++dt) {
+        __syncthreads();
+        #pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          tr[c_row(r, hi) * 36 + kr] = o ? acck[dt][r] : accv[dt][r];
+        }
+        __syncthreads();
+        #pragma unroll
+        for (int rep = 0; rep < 4; ++rep) {
+          const int kk = kr;
+          const int d0 = (hi ? 16 : 0) + rep * 4;
+          if (kw0 + kk < S) {
+            bf16x4_raw w;
+            #pragma unroll
+            for (int j = 0; j < 4; ++j) {
+              w[j] = (short)f32_to_bf16(tr[kk * 36 + d0 + j]);
+            }
+            *(bf16x4_raw*)(out + ((long)b * S + kw0 + kk) * out_rs +
+                           (long)hkv * HD + dt * 32 + d0) = w;
+          }
+        }
+      }
+    }
+  } else {
+    #pragma unroll
+    for (int i = 0; i < 16; ++i) __syncthreads();
+  }
+}
+
 // ---------------------------------------------------------------------------
 // Launchers
 // ---------------------------------------------------------------------------
@@ -1239,6 +1723,24 @@ extern "C" void attn_fwd_launch(const void* q, const void* k, const void* v,
   }
 }
 
+// dK/dV implementation of the backward: 1 = merged (one wave accumulates
+// both outputs), 0 = split (the 8-wave dV/dK role pairs, kept as the
+// comparison build).  Initial value from TORCHX_AMD_DKV_IMPL, read once;
+// the setter switches it at run time so one process can run both.
+static int g_dkv_merged = -1;
+
+extern "C" int attn_bwd_dkv_impl_get() {
+  if (g_dkv_merged < 0) {
+    const char* e = getenv("TORCHX_AMD_DKV_IMPL");
+    g_dkv_merged = (e && strcmp(e, "split") == 0) ? 0 : 1;
+  }
+  return g_dkv_merged;
+}
+
+extern "C" void attn_bwd_dkv_impl_set(int merged) {
+  g_dkv_merged = merged ? 1 : 0;
+}
+
 // ds: the dS scratch (attn_bwd_ds_bytes) selects the streamed dQ kernel;
 // null selects the recompute dQ kernel and the dkv kernel exports nothing.
 // Order pre -> dkv -> dq: the streamed dQ consumes what dkv wrote.
@@ -1262,7 +1764,27 @@ extern "C" void attn_bwd_launch(const void* q, const void* k, const void* v,
     const char* e = getenv("TORCHX_AMD_DKV_FKV");
     dkv_fkv = (e && atoi(e) == 64) ? 64 : 128;
   }
-  if (dkv_fkv == 128 && S % 128 == 0) {
+  if (attn_bwd_dkv_impl_get() == 1) {
+    if (dkv_fkv == 128 && S % 128 == 0) {
+      hipLaunchKernelGGL((attn_bwd_dkv_merged_kernel<128>),
+                         dim3(B * Hkv * nkt), dim3(256), 0, stream,
+                         (const unsigned short*)q, (const unsigned short*)k,
+                         (const unsigned short*)v,
+                         (const unsigned short*)dout, (const float*)lse,
+                         (const float*)delta, (unsigned short*)dk,
+                         (unsigned short*)dv, (char*)ds, B, S, Hq, Hkv,
+                         scale, causal, q_rs, kv_rs, dout_rs, dqkv_kv_rs);
+    } else {
+      hipLaunchKernelGGL((attn_bwd_dkv_merged_kernel<64>),
+                         dim3(B * Hkv * nkt), dim3(256), 0, stream,
+                         (const unsigned short*)q, (const unsigned short*)k,
+                         (const unsigned short*)v,
+                         (const unsigned short*)dout, (const float*)lse,
+                         (const float*)delta, (unsigned short*)dk,
+                         (unsigned short*)dv, (char*)ds, B, S, Hq, Hkv,
+                         scale, causal, q_rs, kv_rs, dout_rs, dqkv_kv_rs);
+    }
+  } else if (dkv_fkv == 128 && S % 128 == 0) {
     hipLaunchKernelGGL((attn_bwd_dkv_kernel<128>), dim3(B * Hkv * nkt),
                        dim3(512), 0, stream, (const unsigned short*)q,
                        (const unsigned short*)k, (const unsigned short*)v,

@@ -29,6 +29,8 @@ void attn_bwd_launch(const void*, const void*, const void*, const void*,
                      void*, int, int, int, int, float, int, long, long, long,
                      long, hipStream_t);
 long attn_bwd_ds_bytes(int, int, int, int);
+int attn_bwd_dkv_impl_get();
+void attn_bwd_dkv_impl_set(int);
 void rope_qkv_launch(const void*, void*, const void*, const void*, long, int,
                      long, int, float, hipStream_t);
 void swiglu_gu_fwd_launch(const void*, void*, long, long, hipStream_t);
@@ -238,6 +240,21 @@ void set_attn_bwd_dq_mode(const std::string& mode) {
 
 std::string get_attn_bwd_dq_mode() {
   return dq_stream_mode() ? "stream" : "recompute";
+}
+
+// dK/dV kernel of the attention backward.  "merged": one wave accumulates
+// both dK and dV for its kv rows (S, P and dP computed once); "split": the
+// 8-wave kernel with separate dV and dK waves.  Both give the same bits.
+// Initial value from TORCHX_AMD_DKV_IMPL (read once by the launcher).
+void set_attn_bwd_dkv_impl(const std::string& impl) {
+  TORCH_CHECK(impl == "merged" || impl == "split",
+              "attn bwd dkv impl must be 'merged' or 'split', got '", impl,
+              "'");
+  attn_bwd_dkv_impl_set(impl == "merged" ? 1 : 0);
+}
+
+std::string get_attn_bwd_dkv_impl() {
+  return attn_bwd_dkv_impl_get() == 1 ? "merged" : "split";
 }
 
 // The scratch is transient HBM on top of the saved activations and grows
@@ -689,6 +706,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("attn_bwd", &attn_bwd);
   m.def("set_attn_bwd_dq_mode", &set_attn_bwd_dq_mode);
   m.def("get_attn_bwd_dq_mode", &get_attn_bwd_dq_mode);
+  m.def("set_attn_bwd_dkv_impl", &set_attn_bwd_dkv_impl);
+  m.def("get_attn_bwd_dkv_impl", &get_attn_bwd_dkv_impl);
   m.def("attn_fwd_qkv", &attn_fwd_qkv);
   m.def("attn_bwd_qkv", &attn_bwd_qkv);
   m.def("rope_qkv", &rope_qkv);
