@@ -13,6 +13,68 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 
 
+def run_batcher(args, model, tokens, fns):
+    """Admit the rows one at a time through PagedBatcher (time to first
+    token per admit, by device events), then time the ragged decode."""
+    from torchx_amd.models.generate import PagedBatcher
+
+    B, S0 = tokens.shape
+    N, P = args.new, args.page_size
+    shared = args.shared_prefix
+    if shared is not None:
+        assert 0 <= shared <= S0
+        tokens[:, :shared] = tokens[0, :shared]
+    max_len = S0 + N + 8
+
+    def batcher():
+        return PagedBatcher(model, B, max_len, B * -(-max_len // P) + 1, P,
+                            prefix_sharing=shared is not None,
+                            prefill_chunk=args.prefill_chunk, **fns)
+
+    # warm every prefill shape (hipBLASLt algo selection) on a batcher
+    # that is thrown away, then time on a fresh one
+    warm = batcher()
+    for b in range(B):
+        warm.admit(b, tokens[b])
+    del warm
+    torch.cuda.synchronize()
+    pb = batcher()
+    free0 = pb.free_pages()
+    ttft = []
+    for b in range(B):
+        start = torch.cuda.Event(enable_timing=True)
+        stop = torch.cuda.Event(enable_timing=True)
+        start.record()
+        pb.admit(b, tokens[b])
+        stop.record()
+        torch.cuda.synchronize()
+        ttft.append(start.elapsed_time(stop))
+    pages_prefill = free0 - pb.free_pages()
+    for _ in range(4):
+        pb.step()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(N - 4):
+        pb.step()
+    torch.cuda.synchronize()
+    t_dec = time.perf_counter() - t0
+    print(json.dumps({
+        "metric": "decode_tokens_per_second",
+        "value": B * (N - 4) / t_dec,
+        "ms_per_decode_step": t_dec / (N - 4) * 1e3,
+        "ttft_ms_per_admit": [round(t, 3) for t in ttft],
+        "shared_tokens": list(pb.shared_tokens),
+        "pages_in_use_after_prefill": pages_prefill,
+        "pages_in_use": free0 - pb.free_pages(),
+        "pages_unshared": B * -(-(S0 + N) // P),
+        "batch": B, "prompt": S0, "new_tokens": N,
+        "model": args.model, "dtype": "bf16", "data": "synthetic",
+        "kv_cache": "paged", "page_size": P, "batcher": True,
+        "prefill_chunk": args.prefill_chunk, "shared_prefix": shared,
+    }))
+    return 0
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--model", default="llama3_8b",
@@ -29,9 +91,25 @@ def main():
     p.add_argument("--page-size", type=int, default=16,
                    help="tokens per page with --paged (power of two, "
                         "16..256)")
+    p.add_argument("--batcher", action="store_true",
+                   help="with --paged: admit the rows one at a time through "
+                        "PagedBatcher and report the time to first token "
+                        "of every admit and the pages in use")
+    p.add_argument("--prefill-chunk", type=int, default=None,
+                   help="implies --batcher: prefill in pieces of at most N "
+                        "tokens (paged prefill attention)")
+    p.add_argument("--shared-prefix", type=int, default=None,
+                   help="implies --batcher with prefix sharing on: all "
+                        "prompts begin with the same N tokens")
     args = p.parse_args()
     if args.paged and args.graph:
         print("--paged has no hipGraph loop", file=sys.stderr)
+        return 1
+    if args.prefill_chunk is not None or args.shared_prefix is not None:
+        args.batcher = True
+    if args.batcher and not args.paged:
+        print("--batcher, --prefill-chunk and --shared-prefix need --paged",
+              file=sys.stderr)
         return 1
 
     from torchx_amd.models.generate import KVCache, PagedKVCache, prefill
@@ -64,6 +142,14 @@ def main():
         decode_step = decode_step_dense
     B, S0, N = args.batch, args.prompt, args.new
     tokens = torch.randint(0, cfg.vocab_size, (B, S0), device=dev)
+    if args.batcher:
+        if moe:
+            from torchx_amd.models.generate_moe import prefill_extend_moe
+            fns = dict(prefill_fn=prefill, decode_fn=decode_step,
+                       extend_fn=prefill_extend_moe)
+        else:
+            fns = {}
+        return run_batcher(args, model, tokens, fns)
     if args.paged:
         # every sequence gets M pages; the table is a seeded permutation
         # of the physical pages so they are not accidentally contiguous

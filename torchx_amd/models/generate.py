@@ -52,7 +52,13 @@ class PageAllocator:
     Page 0 is reserved as the dump page (inactive batch rows read and
     write only its slot 0) and is never handed out. The free list is
     LIFO, so a run is deterministic and a freed page goes straight to the
-    next request."""
+    next request.
+
+    Pages are reference counted for prefix sharing: ``alloc`` hands a page
+    to its first holder, ``share`` adds a holder, ``free`` drops one, and
+    the page returns to the free list when its last holder frees it.
+    Without ``share`` calls every page has one holder and the behaviour is
+    the plain free list's."""
 
     def __init__(self, num_pages: int):
         assert num_pages >= 2, "need the dump page plus one usable page"
@@ -61,6 +67,7 @@ class PageAllocator:
         self._free = list(range(num_pages - 1, 0, -1))
         self._is_free = [True] * num_pages
         self._is_free[0] = False
+        self._refs = [0] * num_pages  # holders per page
 
     @property
     def num_free(self) -> int:
@@ -73,15 +80,31 @@ class PageAllocator:
         pages = [self._free.pop() for _ in range(n)]
         for p in pages:
             self._is_free[p] = False
+            self._refs[p] = 1
         return pages
 
+    def share(self, pages) -> None:
+        """Add one holder to each of ``pages`` (all must be held)."""
+        for p in pages:
+            assert 0 < p < self.num_pages, f"no such page {p}"
+            assert not self._is_free[p], f"page {p} is not held"
+        for p in pages:
+            self._refs[p] += 1
+
+    def refcount(self, p: int) -> int:
+        """Number of holders of page ``p`` (0 for a free page)."""
+        return self._refs[p]
+
     def free(self, pages) -> None:
+        """Drop one holder of each page; the last one frees it."""
         for p in pages:
             assert p != 0, "page 0 is the dump page"
             assert 0 < p < self.num_pages, f"no such page {p}"
             assert not self._is_free[p], f"double free of page {p}"
-            self._is_free[p] = True
-            self._free.append(p)
+            self._refs[p] -= 1
+            if self._refs[p] == 0:
+                self._is_free[p] = True
+                self._free.append(p)
 
 
 @dataclass
@@ -131,6 +154,27 @@ class PagedKVCache:
         kflat.index_copy_(0, slots, k.reshape(B * S, *k.shape[2:]))
         vflat.index_copy_(0, slots, v.reshape(B * S, *v.shape[2:]))
 
+    def store_rows(self, k: torch.Tensor, v: torch.Tensor,
+                   start: int) -> None:
+        """``store_prefix`` at an offset: k, v [B, S, Hkv, D] become the
+        logical rows ``start .. start+S-1`` of the same row(s)."""
+        P = self.page_size
+        B, S = k.shape[:2]
+        t = torch.arange(start, start + S, device=self.block_table.device)
+        table = self.table_rows(B)
+        slots = (table[:, t // P].long() * P + t % P).reshape(-1)
+        kflat = self.kpool.view(-1, *self.kpool.shape[2:])
+        vflat = self.vpool.view(-1, *self.vpool.shape[2:])
+        kflat.index_copy_(0, slots, k.reshape(B * S, *k.shape[2:]))
+        vflat.index_copy_(0, slots, v.reshape(B * S, *v.shape[2:]))
+
+    def table_rows(self, batch: int) -> torch.Tensor:
+        """The block-table row(s) a [batch, S] prefill of this cache
+        addresses, selected as ``store_prefix`` selects them."""
+        r0 = 0 if self.row is None else self.row
+        assert self.row is None or batch == 1
+        return self.block_table[r0:r0 + batch]
+
 
 def _split_qkv(qkv: torch.Tensor, cfg: LlamaConfig):
     B, S, _ = qkv.shape
@@ -162,6 +206,41 @@ def prefill(model: LlamaModel, tokens: torch.Tensor,
             cache.v[:, :S] = v
             cache.length = S
         attn = ops.flash_attention(q, k, v, causal=True)
+        x = x + blk.wo(attn.reshape(B, S, cfg.q_dim))
+        xn = ops.rmsnorm(x, blk.mlp_norm, cfg.rms_eps)
+        x = x + blk.wdown(ops.swiglu_packed(blk.wgu(xn)))
+    x = ops.rmsnorm(x, model.final_norm, cfg.rms_eps)
+    return model.lm_head(x[:, -1])
+
+
+@torch.no_grad()
+def prefill_extend(model: LlamaModel, tokens: torch.Tensor, caches: list,
+                   ctx: int) -> torch.Tensor:
+    """Prefill a piece of a prompt behind ``ctx`` rows the paged caches
+    already hold: tokens [B, S] sit at positions ctx .. ctx+S-1. Their
+    roped K/V go into the pages (``store_rows``) and attention runs over
+    the block table (``ops.paged_prefill_attention``), so the cached rows
+    are neither recomputed nor copied. Returns the last position's logits
+    [B, vocab]. ``ctx = 0`` with the whole prompt is a paged ``prefill``."""
+    cfg = model.cfg
+    B, S = tokens.shape
+    assert ctx >= 0 and S >= 1
+    assert ctx + S <= model.rope_cos.shape[0], "beyond the rope tables"
+    cos = model.rope_cos[ctx:ctx + S]
+    sin = model.rope_sin[ctx:ctx + S]
+    ctx_dev = torch.full((B,), ctx, dtype=torch.int32, device=tokens.device)
+    x = model.embed(tokens)
+    for blk, cache in zip(model.blocks, caches):
+        assert isinstance(cache, PagedKVCache), "paged caches only"
+        assert ctx + S <= cache.block_table.shape[1] * cache.page_size, \
+            "beyond the block table"
+        xn = ops.rmsnorm(x, blk.attn_norm, cfg.rms_eps)
+        q, k, v = _split_qkv(blk.wqkv(xn), cfg)
+        q = ops.rope(q, cos, sin)
+        k = ops.rope(k, cos, sin)
+        cache.store_rows(k, v, ctx)
+        attn = ops.paged_prefill_attention(q, cache.kpool, cache.vpool,
+                                           cache.table_rows(B), ctx_dev)
         x = x + blk.wo(attn.reshape(B, S, cfg.q_dim))
         xn = ops.rmsnorm(x, blk.mlp_norm, cfg.rms_eps)
         x = x + blk.wdown(ops.swiglu_packed(blk.wgu(xn)))
@@ -435,14 +514,45 @@ class PagedBatcher:
     never pages that may already belong to someone else. When a row
     needs a page and the pool is empty, the row is dropped and its index
     appended to ``self.preempted``.
+
+    ``prefill_chunk=N`` prefills a prompt in pieces of at most N tokens
+    through ``extend_fn`` (default ``prefill_extend``; pass
+    ``generate_moe.prefill_extend_moe`` for Mixtral), which bounds the
+    transient activation memory of a long prompt.
+
+    ``prefix_sharing=True`` lets a new request map the pages of a live
+    row whose prompt starts with the same tokens instead of recomputing
+    them. A host-side index maps (parent physical page or -1, the token
+    ids of this page) to a physical page, over pages wholly filled by
+    PROMPT tokens of live rows; ``admit`` walks the prompt's full pages
+    along that chain (at most ``(S0 - 1) // page_size``, so at least one
+    token is computed), takes a reference on the hits, allocates the rest
+    and prefills from the first uncached position.
+    ``self.shared_tokens[row]`` records the hit length. Shared pages are
+    never written again — decode appends at positions >= S0, which lie in
+    a later page than any indexed one, and a retired row parks on page 0
+    — so there is no copy-on-write. A page leaves the index when its last
+    holder frees it; a holder of a child page always holds the parent, so
+    no stale chain survives a page's reuse. With both options off,
+    ``admit`` is the whole-prompt dense-kernel path.
     """
 
     def __init__(self, model, max_batch: int, max_len: int, num_pages: int,
-                 page_size: int = 16, prefill_fn=None, decode_fn=None):
+                 page_size: int = 16, prefill_fn=None, decode_fn=None,
+                 prefix_sharing: bool = False,
+                 prefill_chunk: Optional[int] = None, extend_fn=None):
         self.model = model
         self.cfg = model.cfg
         self._prefill = prefill_fn or prefill
         self._decode = decode_fn or decode_step
+        self._extend = extend_fn or prefill_extend
+        assert prefill_chunk is None or prefill_chunk >= 1
+        self.prefix_sharing = prefix_sharing
+        self.prefill_chunk = prefill_chunk
+        # (parent page or -1, tokens of the page) -> page, and its inverse
+        self._index = {}
+        self._page_key = {}
+        self.shared_tokens = [0] * max_batch
         assert max_len <= self.cfg.max_seq_len, "beyond the rope tables"
         dev = next(model.parameters()).device
         self.device = dev
@@ -480,6 +590,8 @@ class PagedBatcher:
         S0 = prompt.numel()
         assert S0 + 1 < self.max_len
         P = self.page_size
+        if self.prefix_sharing or self.prefill_chunk is not None:
+            return self._admit_extend(row, prompt)
         pages = self.allocator.alloc(-(-(S0 + 1) // P))
         self.pages[row] = pages
         self.block_table[row, :len(pages)] = torch.tensor(
@@ -495,9 +607,66 @@ class PagedBatcher:
         self.active[row] = True
         return nxt[0]
 
+    def _admit_extend(self, row: int, prompt: torch.Tensor) -> torch.Tensor:
+        """``admit`` through ``extend_fn``: map the cached head of the
+        prompt (prefix sharing), prefill the rest in pieces."""
+        S0 = prompt.numel()
+        P = self.page_size
+        toks = prompt.reshape(-1).tolist()
+        hits = []
+        if self.prefix_sharing:
+            parent = -1
+            for j in range((S0 - 1) // P):
+                page = self._index.get((parent, tuple(toks[j * P:(j + 1) * P])))
+                if page is None:
+                    break
+                hits.append(page)
+                parent = page
+        # all-or-nothing, and before anything else changes
+        fresh = self.allocator.alloc(-(-(S0 + 1) // P) - len(hits))
+        self.allocator.share(hits)
+        pages = hits + fresh
+        self.pages[row] = pages
+        self.block_table[row, :len(pages)] = torch.tensor(
+            pages, dtype=torch.int32, device=self.device)
+        ctx = len(hits) * P
+        self.shared_tokens[row] = ctx
+        piece = self.prefill_chunk or (S0 - ctx)
+        row_caches = [c.for_row(row) for c in self.caches]
+        prompt_dev = prompt.reshape(1, S0).to(self.device)
+        while ctx < S0:
+            n = min(piece, S0 - ctx)
+            logits = self._extend(self.model, prompt_dev[:, ctx:ctx + n],
+                                  row_caches, ctx)
+            ctx += n
+        if self.prefix_sharing:
+            # register this row's full prompt pages; stop at a page whose
+            # key another row's page already holds (the cap above can
+            # leave one), so every indexed child's parent is a page this
+            # row holds
+            parent = -1
+            for j in range(S0 // P):
+                key = (parent, tuple(toks[j * P:(j + 1) * P]))
+                if self._index.setdefault(key, pages[j]) != pages[j]:
+                    break
+                self._page_key[pages[j]] = key
+                parent = pages[j]
+        nxt = logits.argmax(-1)
+        self.tok[row, 0] = nxt[0]
+        self.pos[row] = S0
+        self.mask[row] = 1
+        self.pos_host[row] = S0
+        self.active[row] = True
+        return nxt[0]
+
     def retire(self, row: int) -> None:
         """Free the row's pages and park it on the dump page."""
         self.allocator.free(self.pages[row])
+        for p in self.pages[row]:
+            # last holder gone: the page may be reused, forget its content
+            if self.allocator.refcount(p) == 0 and p in self._page_key:
+                del self._index[self._page_key.pop(p)]
+        self.shared_tokens[row] = 0
         self.pages[row] = []
         self.block_table[row] = 0
         self.pos[row] = 0

@@ -26,7 +26,7 @@ from torchx_amd import ops
 from .generate import KVCache, PagedKVCache
 from .mixtral import MixtralModel, MoELayer
 
-__all__ = ["prefill_moe", "decode_step_moe", "generate_moe", "KVCache"]
+__all__ = ["prefill_moe", "prefill_extend_moe", "decode_step_moe", "generate_moe", "KVCache"]
 
 
 def _moe_mlp_decode(moe: MoELayer, x: torch.Tensor) -> torch.Tensor:
@@ -78,6 +78,42 @@ def prefill_moe(model: MixtralModel, tokens: torch.Tensor,
             cache.v[:, :S] = v
             cache.length = S
         attn = ops.flash_attention(q, k, v, causal=True)
+        x = x + blk.wo(attn.reshape(B, S, cfg.q_dim))
+        xn = ops.rmsnorm(x, blk.mlp_norm, cfg.rms_eps)
+        x = x + blk.moe(xn)
+    x = ops.rmsnorm(x, model.final_norm, cfg.rms_eps)
+    return model.lm_head(x[:, -1])
+
+
+@torch.no_grad()
+def prefill_extend_moe(model: MixtralModel, tokens: torch.Tensor,
+                       caches: list, ctx: int) -> torch.Tensor:
+    """generate.prefill_extend with the MoE MLP: tokens [B, S] at
+    positions ctx .. ctx+S-1 behind ``ctx`` rows the paged caches already
+    hold; returns last-position logits [B, vocab]."""
+    cfg = model.cfg
+    B, S = tokens.shape
+    assert ctx >= 0 and S >= 1
+    assert ctx + S <= model.rope_cos.shape[0], "beyond the rope tables"
+    cos = model.rope_cos[ctx:ctx + S]
+    sin = model.rope_sin[ctx:ctx + S]
+    ctx_dev = torch.full((B,), ctx, dtype=torch.int32, device=tokens.device)
+    x = model.embed(tokens)
+    for blk, cache in zip(model.blocks, caches):
+        assert isinstance(cache, PagedKVCache), "paged caches only"
+        assert ctx + S <= cache.block_table.shape[1] * cache.page_size, \
+            "beyond the block table"
+        xn = ops.rmsnorm(x, blk.attn_norm, cfg.rms_eps)
+        qkv = blk.wqkv(xn)
+        q, k, v = qkv.split([cfg.q_dim, cfg.kv_dim, cfg.kv_dim], dim=-1)
+        q = ops.rope(q.reshape(B, S, cfg.num_heads, cfg.head_dim)
+                     .contiguous(), cos, sin)
+        k = ops.rope(k.reshape(B, S, cfg.num_kv_heads, cfg.head_dim)
+                     .contiguous(), cos, sin)
+        v = v.reshape(B, S, cfg.num_kv_heads, cfg.head_dim).contiguous()
+        cache.store_rows(k, v, ctx)
+        attn = ops.paged_prefill_attention(q, cache.kpool, cache.vpool,
+                                           cache.table_rows(B), ctx_dev)
         x = x + blk.wo(attn.reshape(B, S, cfg.q_dim))
         xn = ops.rmsnorm(x, blk.mlp_norm, cfg.rms_eps)
         x = x + blk.moe(xn)

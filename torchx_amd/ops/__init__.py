@@ -634,6 +634,34 @@ def paged_decode_attention(q: torch.Tensor, kpool: torch.Tensor,
     return torch.cat(outs, dim=0)
 
 
+def paged_prefill_attention(q: torch.Tensor, kpool: torch.Tensor,
+                            vpool: torch.Tensor, block_table: torch.Tensor,
+                            ctx: torch.Tensor,
+                            scale: Optional[float] = None) -> torch.Tensor:
+    """Causal attention of a prompt chunk behind a cached prefix. q
+    [B, S, Hq, D] holds the rows at logical positions ``ctx[b] ..
+    ctx[b]+S-1`` of sequence b; the pools already hold that sequence's
+    ``ctx[b] + S`` rows (the chunk's own K/V included), row t at
+    ``pool[block_table[b, t // P], t % P]``. Row i attends t <= ctx[b] + i
+    -> o [B, S, Hq, D]. ``ctx`` is int32 [B]. On the GPU (D = 128), for
+    ``ctx[b] % 128 == 0`` the result is bit-identical to rows ``ctx[b]:``
+    of ``flash_attention`` (causal) over the gathered dense sequence."""
+    if scale is None:
+        scale = 1.0 / math.sqrt(q.shape[-1])
+    if _on_gpu(q):
+        return hip_ops().paged_prefill_attn(q.contiguous(), kpool, vpool,
+                                            block_table, ctx.contiguous(),
+                                            scale)
+    S = q.shape[1]
+    outs = []
+    for b in range(q.shape[0]):
+        c = int(ctx[b].item())
+        outs.append(reference.attention_prefix(
+            q[b:b + 1], reference.paged_gather(kpool, block_table[b], c + S),
+            reference.paged_gather(vpool, block_table[b], c + S), c, scale))
+    return torch.cat(outs, dim=0)
+
+
 def paged_decode_rope_cache(qkv: torch.Tensor, kpool: torch.Tensor,
                             vpool: torch.Tensor, block_table: torch.Tensor,
                             cos: torch.Tensor, sin: torch.Tensor,

@@ -22,9 +22,10 @@
 //  * T1 XCD swizzle: blocks streaming the same (batch, kv-head) tensors
 //    land on one XCD so the stream is L2-resident (the kernels are
 //    otherwise HBM-bound at ~128 FLOP/B).
-//  * Forward block size is S-dependent: 4 waves below S=8192, 8 waves at
-//    or above (staging amortizes over 2x compute once causal wave-skew
-//    is relatively small).
+//  * Forward block size is 4 waves at every length (the 8-wave variant
+//    stays selectable for re-measurement, see attn_fwd_launch).
+//  * paged_prefill_attn_kernel: the 4-wave forward over a block-table KV
+//    cache, for a chunk of query rows behind an already cached prefix.
 //  * Backward is FA2-style without atomics: preprocess delta =
 //    rowsum(dO*O); ONE dK+dV kernel, 4 waves at one wave per SIMD, in
 //    which a wave accumulates both dK and dV for its 32 kv rows (S, P and
@@ -488,6 +489,283 @@ attn_fwd_kernel(const unsigned short* __restrict__ q,
   if (!hi) {
     // lse stays in the natural-log domain for the backward kernels
     lse[((long)b * Hq + hq) * S + q_row] = (m_run + __log2f(l_run)) * LN2;
+  }
+}
+
+// ---------------------------------------------------------------------------
+// Paged prefill: a chunk of S query rows at logical positions
+// ctx[b] .. ctx[b]+S-1 over a block-table KV cache that already holds
+// L = ctx[b] + S rows (the chunk's own K/V are stored before the launch).
+//
+//   q            [B, S, Hq, 128] bf16
+//   kpool/vpool  [num_pages, P, Hkv, 128] bf16, P a power of two, 16..256
+//   bt           int32 [B, M]; logical row t of sequence b is
+//                pool[bt[b][t / P]][t % P][hkv][:]
+//   ctx          int32 [B]
+//   o            [B, S, Hq, 128] bf16       (no lse: inference only)
+//
+// This is attn_fwd_kernel<4> (causal) with two changes. (1) The staging
+// source row goes through the table. A wave stages the 16 consecutive,
+// 16-aligned logical rows [kv0 + 16w, +16) of a tile, which lie in ONE
+// page for every P >= 16, so a tile costs each lane one table entry; rows
+// at or past L read row L-1 (as the dense kernel clamps to S-1) through
+// the entry of page (L-1)/P fetched once. The entry for the tile after
+// next is fetched while the next tile's loads are issued, so no K/V load
+// waits on a table load of its own iteration. (2) The causal diagonal is
+// shifted by ctx: q row i sees keys t <= ctx + i.
+//
+// The LDS images, the tile sequence, the MFMA order and the softmax are
+// the dense kernel's expressions in the dense kernel's order. Hence, for
+// ctx[b] % 128 == 0, row i of the output is bit-identical to row
+// ctx[b] + i of attn_fwd_kernel<4> (causal) over the gathered dense
+// sequence of length ctx[b] + S: the block holds the same 128 q rows, its
+// waves the same 32, and every wave walks the same tiles. For any other
+// ctx the grouping of q rows into waves differs, the __all of the
+// defer-max decision sees other rows, and only the tolerance against an
+// fp32 reference holds.
+//
+// No table or ctx content can address outside the pools or the table:
+// ctx is clamped to [0, M*P] and L to [1, M*P], table indices are taken
+// from rows < L (so < M), every entry read is clamped to [0, num_pages),
+// and pool offsets are 64-bit.
+// ---------------------------------------------------------------------------
+
+// Table entry of the page holding the wave's 16-row staging group of the
+// tile at kv0 (the row is clamped into the sequence, so the index is < M).
+// The raw entry is carried to the iteration that uses it and clamped
+// there (paged_page_base), so nothing waits on this load where it issues.
+__device__ __forceinline__ int paged_group_entry(
+    const int* __restrict__ bt_row, int kv0, int L, int logP) {
+  const int wave = threadIdx.x / 64;
+  const int g0 = min(kv0 + wave * (FKV / 4), L - 1);
+  return bt_row[g0 >> logP];
+}
+
+// Physical first row of a page, the table entry clamped to [0, num_pages).
+__device__ __forceinline__ long paged_page_base(int entry, int num_pages,
+                                                int logP) {
+  return (long)min(max(entry, 0), num_pages - 1) << logP;
+}
+
+// stage_k_glds<4> with the source row looked up: same lane -> (row,
+// colbyte) map, same LDS image.  `pb` points at this kv head's column of
+// pool row 0; `grp_base` is the page base of this tile's group, `last_row`
+// the physical row of logical row L-1.
+__device__ __forceinline__ void stage_paged_glds(
+    const unsigned short* __restrict__ pb, int kv0, long stride_elems,
+    int L, int pmask, long grp_base, long last_row, char* img) {
+  const int wave = threadIdx.x / 64;
+  const int lane = threadIdx.x & 63;
+  #pragma unroll
+  for (int j = 0; j < (FKV / 4) / 4; ++j) {
+    const int i = wave * ((FKV / 4) / 4) + j;
+    const int row = i * 4 + (lane >> 4);
+    const int colbyte = ((lane & 15) * 16) ^ ((row & 15) << 4);
+    const int t = kv0 + row;
+    long srow = grp_base + (t & pmask);
+    if (t >= L) srow = last_row;
+    const char* src = (const char*)(pb + srow * stride_elems) + colbyte;
+    __builtin_amdgcn_global_load_lds(
+        (const __attribute__((address_space(1))) unsigned int*)src,
+        (__attribute__((address_space(3))) unsigned int*)(img + i * 1024),
+        16, 0, 0);
+  }
+}
+
+__global__ void __launch_bounds__(256, 2)
+paged_prefill_attn_kernel(const unsigned short* __restrict__ q,
+                          const unsigned short* __restrict__ kpool,
+                          const unsigned short* __restrict__ vpool,
+                          unsigned short* __restrict__ o,
+                          const int* __restrict__ bt,   // [B, M]
+                          const int* __restrict__ ctx,  // [B]
+                          int B, int S, int Hq, int Hkv, int num_pages,
+                          int logP, int M, float scale) {
+  __shared__ __align__(16) char smem[4 * KIMG_BYTES];
+
+  const int BQ = 4 * QBLK;
+  const int nqt = (S + BQ - 1) / BQ;
+  const int G = Hq / Hkv;
+  int b, hq, qt;
+  map_block_fwd(B, Hq, Hkv, nqt, G, &b, &hq, &qt);
+  const int hkv = hq / G;
+
+  const int wave = threadIdx.x / 64;
+  const int lane = threadIdx.x & 63;
+  const bool hi = lane >= 32;
+  const int qr = lane & 31;
+
+  // cached rows before the chunk, and the sequence length; compare before
+  // adding so a garbage ctx cannot overflow
+  const int cap = M << logP;
+  const int c0 = min(max(ctx[b], 0), cap);
+  const int L = (S > cap - c0) ? cap : c0 + S;
+  const int pmask = (1 << logP) - 1;
+  const int* bt_row = bt + (long)b * M;
+
+  const long q_seq_stride = (long)Hq * HD;
+  const long kv_seq_stride = (long)Hkv * HD;
+  const unsigned short* qb = q + (long)b * S * q_seq_stride + (long)hq * HD;
+  const unsigned short* kb = kpool + (long)hkv * HD;
+  const unsigned short* vb = vpool + (long)hkv * HD;
+
+  const int q0_blk = qt * BQ;
+  const int qw0 = q0_blk + wave * QBLK;       // wave's first q row
+  const long q_row = qw0 + qr;                 // this lane's q row
+  const bool wave_active = qw0 < S;
+
+  // Q fragments in registers: chunk c covers d in [16c, 16c+16)
+  mbf16x8 qfrag[8];
+  {
+    const long row = (q_row < S) ? q_row : (S - 1);
+    const unsigned short* qp = qb + row * q_seq_stride + (hi ? 8 : 0);
+    #pragma unroll
+    for (int c = 0; c < 8; ++c) {
+      qfrag[c] = __builtin_bit_cast(mbf16x8, *(const ushort8*)(qp + c * 16));
+    }
+  }
+
+  f32x16 acc_o[4] = {};
+  float m_run = -3.0e38f, l_run = 0.f;   // m in exp2 domain
+  const float sc2 = scale * LOG2E;
+
+  const int kv_limit = min(L, c0 + q0_blk + BQ);
+  const int ntiles = (kv_limit + FKV - 1) / FKV;
+  const int qw_max = min(qw0 + QBLK - 1, S - 1);
+
+  char* k0 = smem;                       // K tile t   (cur)
+  char* k1 = smem + KIMG_BYTES;          // K tile t+1 (in flight)
+  char* vcur = smem + 2 * KIMG_BYTES;    // V natural cur
+  char* vnxt = smem + 3 * KIMG_BYTES;    // V natural nxt
+
+  // physical row of logical row L-1 (where rows past the end read)
+  const long last_row =
+      paged_page_base(bt_row[(L - 1) >> logP], num_pages, logP) +
+      ((L - 1) & pmask);
+
+  // prologue: glds K0 + V0 natural; table entry of tile 1
+  int ent_nxt = paged_group_entry(bt_row, FKV, L, logP);
+  {
+    const long base0 = paged_page_base(
+        paged_group_entry(bt_row, 0, L, logP), num_pages, logP);
+    stage_paged_glds(kb, 0, kv_seq_stride, L, pmask, base0, last_row, k0);
+    stage_paged_glds(vb, 0, kv_seq_stride, L, pmask, base0, last_row, vcur);
+  }
+  asm volatile("s_waitcnt vmcnt(0)");
+  __syncthreads();
+
+  for (int t = 0; t < ntiles; ++t) {
+    const int kv0 = t * FKV;
+    const bool has_next = (t + 1) < ntiles;
+    if (has_next) {
+      // issue next K/V glds BEFORE compute (T14), through the entry
+      // fetched one iteration ago; the entry of tile t+2 goes out with
+      // them and is first looked at in the next iteration
+      const long base = paged_page_base(ent_nxt, num_pages, logP);
+      ent_nxt = paged_group_entry(bt_row, kv0 + 2 * FKV, L, logP);
+      stage_paged_glds(kb, kv0 + FKV, kv_seq_stride, L, pmask, base,
+                       last_row, k1);
+      stage_paged_glds(vb, kv0 + FKV, kv_seq_stride, L, pmask, base,
+                       last_row, vnxt);
+    }
+
+    const bool needed = wave_active && (kv0 <= c0 + qw_max);
+    if (needed) {
+      // S^T[k, q] = K . Q^T over both 32-row k sub-tiles (T5)
+      f32x16 acc0 = {}, acc1 = {};
+      __builtin_amdgcn_s_setprio(1);
+      #pragma unroll
+      for (int c = 0; c < 8; ++c) {
+        acc0 = mfma32(kimg_frag(k0, 0, c), qfrag[c], acc0);
+        acc1 = mfma32(kimg_frag(k0, 1, c), qfrag[c], acc1);
+      }
+      __builtin_amdgcn_s_setprio(0);
+
+      float sv[32];
+      #pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        sv[r] = acc0[r] * sc2;
+        sv[16 + r] = acc1[r] * sc2;
+      }
+      const bool mask_tile =
+          (kv0 + FKV - 1 > c0 + qw0) || (kv0 + FKV > L) || (q_row >= S);
+      if (mask_tile) {
+        #pragma unroll
+        for (int r = 0; r < 32; ++r) {
+          const long kg = kv0 + (r >> 4) * 32 + c_row(r & 15, hi);
+          if (kg >= L || q_row >= S || kg > c0 + q_row) {
+            sv[r] = -3.0e38f;
+          }
+        }
+      }
+
+      // online softmax, exp2 domain, T13 defer-max (see attn_fwd_kernel)
+      float m_tile = sv[0];
+      #pragma unroll
+      for (int r = 1; r < 32; ++r) m_tile = fmaxf(m_tile, sv[r]);
+      m_tile = fmaxf(m_tile, __shfl_xor(m_tile, 32, 64));
+      const float THR2 = 11.54f;  // 8 * log2(e)
+      if (!__all(m_tile - m_run <= THR2)) {
+        const float m_new = fmaxf(m_run, m_tile);
+        const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);
+        l_run *= alpha;
+        m_run = m_new;
+        #pragma unroll
+        for (int dt = 0; dt < 4; ++dt) {
+          #pragma unroll
+          for (int r = 0; r < 16; ++r) acc_o[dt][r] *= alpha;
+        }
+      }
+
+      float row_sum = 0.f;
+      #pragma unroll
+      for (int r = 0; r < 32; ++r) {
+        sv[r] = __builtin_amdgcn_exp2f(sv[r] - m_run);  // sv becomes P
+        row_sum += sv[r];
+      }
+      row_sum += __shfl_xor(row_sum, 32, 64);
+      l_run += row_sum;
+
+      mbf16x8 pf[4];
+      cvals_to_frags(sv, hi, &pf[0], &pf[1]);
+      cvals_to_frags(sv + 16, hi, &pf[2], &pf[3]);
+
+      // O^T[d, q] += V^T . P  (hardware transpose read, T10)
+      __builtin_amdgcn_s_setprio(1);
+      #pragma unroll
+      for (int dt = 0; dt < 4; ++dt) {
+        #pragma unroll
+        for (int ks = 0; ks < 4; ++ks) {
+          acc_o[dt] = mfma32(nat_tr_frag(vcur, ks, dt), pf[ks], acc_o[dt]);
+        }
+      }
+      __builtin_amdgcn_s_setprio(0);
+    }
+
+    if (has_next) {
+      asm volatile("s_waitcnt vmcnt(0)");  // own K/V glds landed
+      __syncthreads();   // everyone done reading cur; nxt visible
+      char* tk = k0; k0 = k1; k1 = tk;
+      char* tv = vcur; vcur = vnxt; vnxt = tv;
+    }
+  }
+
+  if (!wave_active || q_row >= S) return;
+
+  const float inv_l = (l_run > 0.f) ? 1.0f / l_run : 0.f;
+  unsigned short* ob = o + (((long)b * S + q_row) * Hq + hq) * HD;
+  #pragma unroll
+  for (int dt = 0; dt < 4; ++dt) {
+    #pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      // regs 4g..4g+3 are consecutive d: d = dt*32 + 8g + 4*hi + (0..3)
+      bf16x4_raw w;
+      #pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        w[j] = (short)f32_to_bf16(acc_o[dt][4 * g + j] * inv_l);
+      }
+      *(bf16x4_raw*)(ob + dt * 32 + 8 * g + 4 * (hi ? 1 : 0)) = w;
+    }
   }
 }
 
@@ -1721,6 +1999,19 @@ extern "C" void attn_fwd_launch(const void* q, const void* k, const void* v,
                        (unsigned short*)o, (float*)lse, B, S, Hq, Hkv,
                        scale, causal, q_rs, kv_rs);
   }
+}
+
+extern "C" void paged_prefill_attn_launch(
+    const void* q, const void* kpool, const void* vpool, void* o,
+    const void* bt, const void* ctx, int B, int S, int Hq, int Hkv,
+    int num_pages, int logP, int M, float scale, hipStream_t stream) {
+  const int nqt = (S + 4 * QBLK - 1) / (4 * QBLK);
+  hipLaunchKernelGGL(paged_prefill_attn_kernel, dim3(B * Hq * nqt), dim3(256),
+                     0, stream, (const unsigned short*)q,
+                     (const unsigned short*)kpool,
+                     (const unsigned short*)vpool, (unsigned short*)o,
+                     (const int*)bt, (const int*)ctx, B, S, Hq, Hkv,
+                     num_pages, logP, M, scale);
 }
 
 // dK/dV implementation of the backward: 1 = merged (one wave accumulates

@@ -65,6 +65,9 @@ void paged_decode_rope_cache_launch(const void*, void*, void*, void*,
                                     const void*, const void*, const void*,
                                     const void*, int, int, int, int, int,
                                     int, int, hipStream_t);
+void paged_prefill_attn_launch(const void*, const void*, const void*, void*,
+                               const void*, const void*, int, int, int, int,
+                               int, int, int, float, hipStream_t);
 }
 
 namespace {
@@ -643,6 +646,33 @@ at::Tensor paged_decode_rope_cache(at::Tensor qkv, at::Tensor kpool,
   return q;
 }
 
+// q [B, S, Hq, 128]: a chunk of S query rows at logical positions
+// ctx[b] .. ctx[b]+S-1, attending the ctx[b]+S rows the pools already hold
+// for sequence b (causal). Returns o [B, S, Hq, 128].
+at::Tensor paged_prefill_attn(at::Tensor q, at::Tensor kpool,
+                              at::Tensor vpool, at::Tensor bt, at::Tensor ctx,
+                              double scale) {
+  check_bf16(q, "q");
+  TORCH_CHECK(q.dim() == 4 && q.size(3) == 128,
+              "q must be [B, S, Hq, 128]");
+  const int B = q.size(0), Hq = q.size(2);
+  TORCH_CHECK(q.size(1) >= 1 && q.size(1) < (1L << 30), "need 1 <= S < 2^30");
+  const int S = q.size(1);
+  const int logP = check_paged(kpool, vpool, bt, ctx, B);
+  TORCH_CHECK(ctx.dim() == 1, "ctx must be int32 [B]");
+  const int num_pages = kpool.size(0), Hkv = kpool.size(2);
+  const int M = bt.size(1);
+  TORCH_CHECK(Hq % Hkv == 0, "GQA group mismatch");
+  const long nqt = (S + 127) / 128;
+  TORCH_CHECK((long)B * Hq * nqt < (1L << 31), "grid too large");
+  auto o = at::empty_like(q);
+  paged_prefill_attn_launch(q.data_ptr(), kpool.data_ptr(), vpool.data_ptr(),
+                            o.data_ptr(), bt.data_ptr(), ctx.data_ptr(), B, S,
+                            Hq, Hkv, num_pages, logP, M, (float)scale,
+                            cur_stream());
+  return o;
+}
+
 // ---- fused residual add + rmsnorm (inference) ------------------------------
 // s = x + res, y = rmsnorm(s) * w; returns (s, y). res omitted -> plain
 // rmsnorm (s aliases x).
@@ -727,6 +757,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("pos_dev") = c10::nullopt);
   m.def("paged_decode_attn", &paged_decode_attn);
   m.def("paged_decode_rope_cache", &paged_decode_rope_cache);
+  m.def("paged_prefill_attn", &paged_prefill_attn);
   m.def("rmsnorm_res", &rmsnorm_res,
         py::arg("x"), py::arg("res"), py::arg("w"), py::arg("eps"));
 }

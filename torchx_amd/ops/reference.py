@@ -67,6 +67,31 @@ def attention(
     return o.permute(0, 2, 1, 3).contiguous().to(q.dtype)
 
 
+def attention_prefix(
+    q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, ctx: int,
+    scale: Optional[float] = None,
+) -> torch.Tensor:
+    """Causal GQA attention of a chunk behind a cached prefix, fp32 math:
+    q [B,S,Hq,D] holds the rows at positions ctx .. ctx+S-1 of sequences
+    whose keys/values k, v [B,ctx+S,Hkv,D] are all known; row i attends
+    t <= ctx + i. Any D; returns bf16-like q.dtype [B,S,Hq,D]."""
+    B, S, Hq, D = q.shape
+    T, Hkv = k.shape[1], k.shape[2]
+    assert T == ctx + S, (T, ctx, S)
+    if scale is None:
+        scale = 1.0 / math.sqrt(D)
+    g = Hq // Hkv
+    qf = q.float().permute(0, 2, 1, 3)                       # [B,Hq,S,D]
+    kf = k.float().permute(0, 2, 1, 3).repeat_interleave(g, dim=1)
+    vf = v.float().permute(0, 2, 1, 3).repeat_interleave(g, dim=1)
+    s = torch.matmul(qf, kf.transpose(-1, -2)) * scale       # [B,Hq,S,T]
+    mask = torch.ones(S, T, dtype=torch.bool, device=q.device).triu(ctx + 1)
+    s = s.masked_fill(mask, float("-inf"))
+    p = torch.softmax(s, dim=-1)
+    o = torch.matmul(p, vf)
+    return o.permute(0, 2, 1, 3).contiguous().to(q.dtype)
+
+
 def attention_lse(
     q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
     causal: bool = True, scale: Optional[float] = None,
