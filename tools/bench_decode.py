@@ -75,6 +75,109 @@ def run_batcher(args, model, tokens, fns):
     return 0
 
 
+def _spread(ts):
+    ts = sorted(ts)
+    return ts[len(ts) // 2], ts[0], ts[-1]
+
+
+def run_admit_many(args, model, tokens, fns, dense_prefill, rounds=5):
+    """Time to first token of all rows: one ``admit_many`` call against
+    the one-at-a-time ``admit`` loop and, for scale, the dense [B, S]
+    ``prefill``. Each is warmed on throw-away state, then the three
+    alternate within every round on fresh batchers; device-event times,
+    median and [min..max] over the rounds. Then the ragged decode of the
+    last ``admit_many`` batcher is timed as ``run_batcher`` does."""
+    from torchx_amd.models.generate import KVCache, PagedBatcher
+
+    B, S0 = tokens.shape
+    N, P = args.new, args.page_size
+    shared = args.shared_prefix
+    if shared is not None:
+        assert 0 <= shared <= S0
+        tokens[:, :shared] = tokens[0, :shared]
+    max_len = S0 + N + 8
+    rows = list(range(B))
+    prompts = [tokens[b] for b in rows]
+
+    def batcher():
+        return PagedBatcher(model, B, max_len, B * -(-max_len // P) + 1, P,
+                            prefix_sharing=shared is not None,
+                            prefill_chunk=args.prefill_chunk, **fns)
+
+    def timed(fn):
+        start = torch.cuda.Event(enable_timing=True)
+        stop = torch.cuda.Event(enable_timing=True)
+        start.record()
+        fn()
+        stop.record()
+        torch.cuda.synchronize()
+        return start.elapsed_time(stop)
+
+    def many(pb):
+        return lambda: pb.admit_many(rows, prompts)
+
+    def loop(pb):
+        def go():
+            for b in rows:
+                pb.admit(b, prompts[b])
+        return go
+
+    def dense():
+        caches = [KVCache.empty(model.cfg, B, max_len, tokens.device)
+                  for _ in range(model.cfg.num_layers)]
+        return lambda: dense_prefill(model, tokens, caches)
+
+    for make in (many, loop):                    # warm both (GEMM shapes)
+        make(batcher())()
+    dense()()
+    torch.cuda.synchronize()
+    t_many, t_loop, t_dense = [], [], []
+    pb = None
+    for _ in range(rounds):
+        del pb
+        t_loop.append(timed(loop(batcher())))
+        t_dense.append(timed(dense()))
+        pb = batcher()
+        free0 = pb.free_pages()
+        t_many.append(timed(many(pb)))
+    pages_prefill = free0 - pb.free_pages()
+    for _ in range(4):
+        pb.step()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(N - 4):
+        pb.step()
+    torch.cuda.synchronize()
+    t_dec = time.perf_counter() - t0
+
+    def stats(ts):
+        med, lo, hi = _spread(ts)
+        return {"ms": round(med, 3), "ms_min": round(lo, 3),
+                "ms_max": round(hi, 3),
+                "prefill_tokens_per_second": round(B * S0 / med * 1e3)}
+
+    print(json.dumps({
+        "metric": "decode_tokens_per_second",
+        "value": B * (N - 4) / t_dec,
+        "ms_per_decode_step": t_dec / (N - 4) * 1e3,
+        "ttft_admit_many": stats(t_many),
+        "ttft_admit_loop": stats(t_loop),
+        "ttft_dense_prefill": stats(t_dense),
+        "admit_many_speedup": round(_spread(t_loop)[0] / _spread(t_many)[0],
+                                    3),
+        "rounds": rounds,
+        "shared_tokens": list(pb.shared_tokens),
+        "pages_in_use_after_prefill": pages_prefill,
+        "pages_in_use": free0 - pb.free_pages(),
+        "batch": B, "prompt": S0, "new_tokens": N,
+        "model": args.model, "dtype": "bf16", "data": "synthetic",
+        "kv_cache": "paged", "page_size": P, "batcher": True,
+        "admit_many": True,
+        "prefill_chunk": args.prefill_chunk, "shared_prefix": shared,
+    }))
+    return 0
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--model", default="llama3_8b",
@@ -101,15 +204,22 @@ def main():
     p.add_argument("--shared-prefix", type=int, default=None,
                    help="implies --batcher with prefix sharing on: all "
                         "prompts begin with the same N tokens")
+    p.add_argument("--admit-many", action="store_true",
+                   help="implies --batcher: admit all rows in ONE "
+                        "admit_many call (packed ragged prefill) and report "
+                        "its time next to the one-at-a-time loop and the "
+                        "dense prefill, alternated in this process")
     args = p.parse_args()
+    if args.admit_many:
+        args.batcher = True
     if args.paged and args.graph:
         print("--paged has no hipGraph loop", file=sys.stderr)
         return 1
     if args.prefill_chunk is not None or args.shared_prefix is not None:
         args.batcher = True
     if args.batcher and not args.paged:
-        print("--batcher, --prefill-chunk and --shared-prefix need --paged",
-              file=sys.stderr)
+        print("--batcher, --prefill-chunk, --shared-prefix and --admit-many "
+              "need --paged", file=sys.stderr)
         return 1
 
     from torchx_amd.models.generate import KVCache, PagedKVCache, prefill
@@ -144,11 +254,16 @@ def main():
     tokens = torch.randint(0, cfg.vocab_size, (B, S0), device=dev)
     if args.batcher:
         if moe:
-            from torchx_amd.models.generate_moe import prefill_extend_moe
+            from torchx_amd.models.generate_moe import (
+                prefill_extend_moe, prefill_ragged_moe,
+            )
             fns = dict(prefill_fn=prefill, decode_fn=decode_step,
-                       extend_fn=prefill_extend_moe)
+                       extend_fn=prefill_extend_moe,
+                       ragged_fn=prefill_ragged_moe)
         else:
             fns = {}
+        if args.admit_many:
+            return run_admit_many(args, model, tokens, fns, prefill)
         return run_batcher(args, model, tokens, fns)
     if args.paged:
         # every sequence gets M pages; the table is a seeded permutation

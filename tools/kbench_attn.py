@@ -96,6 +96,129 @@ def bench_paged_prefill(iters, rounds=5):
                   f"bit-identical {same}")
 
 
+def _alternate(fns, n, rounds):
+    """Time the callables in turn within each round; per callable the
+    (median, min, max) ms over the rounds."""
+    for _ in range(5):
+        for fn in fns.values():
+            fn()
+    ts = {name: [] for name in fns}
+    for _ in range(rounds):
+        for name, fn in fns.items():
+            ts[name].append(time_events(fn, n))
+    out = {}
+    for name, t in ts.items():
+        t.sort()
+        out[name] = (t[rounds // 2], t[0], t[-1])
+    return out
+
+
+def _show(label, res, base):
+    parts = [f"{name} {m:.4f} ms [{lo:.4f}..{hi:.4f}]"
+             for name, (m, lo, hi) in res.items()]
+    ratios = [f"{name}/{base} {res[name][0] / res[base][0]:.3f}"
+              for name in res if name != base]
+    print(f"{label}: " + " | ".join(parts + ratios))
+
+
+def bench_paged_prefill_ragged(iters, rounds=5):
+    """paged_prefill_attn_ragged (tiles heaviest first, and sequence by
+    sequence) against paged_prefill_attn on the same pools, ctx = 0,
+    H32/8, P16: at equal lengths (B4 S4096, B4 S512) on the same data; at
+    q_lens [4096, 512, 512, 64] against a loop of the existing op per
+    sequence and against the existing op padded to the longest. Then the
+    fused rope + page append against the dispatches it replaces at
+    T = 2048. The candidates alternate within each round."""
+    hip = ops.hip_ops(required=True)
+    dev = torch.device("cuda", 0)
+    Hq, Hkv, D, P = 32, 8, 128, 16
+    scale = D ** -0.5
+    for q_lens in ([4096] * 4, [512] * 4, [4096, 512, 512, 64]):
+        torch.manual_seed(0)
+        B, S = len(q_lens), max(q_lens)
+        M = S // P                       # every row mapped: padding is legal
+        g = torch.Generator().manual_seed(0)
+        table = (torch.randperm(B * M, generator=g) + 1).to(torch.int32)
+        table = table.reshape(B, M).to(dev)
+        kpool = torch.randn(B * M + 1, P, Hkv, D, device=dev,
+                            dtype=torch.bfloat16)
+        vpool = torch.randn_like(kpool)
+        qpad = torch.randn(B, S, Hq, D, device=dev, dtype=torch.bfloat16)
+        q = torch.cat([qpad[b, :n] for b, n in enumerate(q_lens)])
+        ctx = torch.zeros(B, dtype=torch.int32, device=dev)
+        plans = {h: ops.RaggedPlan(q_lens, dev, heavy_first=h)
+                 for h in (True, False)}
+        per_seq = [(qpad[b:b + 1, :n].contiguous(), table[b:b + 1],
+                    ctx[b:b + 1]) for b, n in enumerate(q_lens)]
+
+        def ragged(heavy):
+            return lambda: hip.paged_prefill_attn_ragged(
+                q, kpool, vpool, table, ctx, plans[heavy].tiles, scale)
+
+        def padded():
+            return hip.paged_prefill_attn(qpad, kpool, vpool, table, ctx,
+                                          scale)
+
+        def loop():
+            return [hip.paged_prefill_attn(qb, kpool, vpool, tb, cb, scale)
+                    for qb, tb, cb in per_seq]
+
+        fns = {"ragged_heavy_first": ragged(True),
+               "ragged_in_order": ragged(False)}
+        equal = len(set(q_lens)) == 1
+        if equal:
+            fns["existing"] = padded
+            same = torch.equal(ragged(True)().reshape(qpad.shape), padded())
+        else:
+            fns["loop"] = loop
+            fns["padded"] = padded
+            same = torch.equal(ragged(True)(),
+                               torch.cat([o[0] for o in loop()]))
+        n = iters if S >= 4096 else iters * 20
+        res = _alternate(fns, n, rounds)
+        _show(f"q_lens {q_lens} H{Hq}/{Hkv} P{P} bit-identical {same}", res,
+              "existing" if equal else "loop")
+
+    # fused rope + page append against split + 3 contiguous copies +
+    # 2 ropes + 2 index_copy_ (what prefill_extend runs per layer)
+    T = 2048
+    torch.manual_seed(0)
+    qkv = torch.randn(T, (Hq + 2 * Hkv) * D, device=dev,
+                      dtype=torch.bfloat16)
+    ang = torch.arange(T).float()[:, None] * (
+        1.0 / 10000.0 ** (torch.arange(0, D, 2).float() / D))[None]
+    cos, sin = ang.cos().to(dev), ang.sin().to(dev)
+    pos = torch.arange(T, dtype=torch.int32, device=dev)
+    g = torch.Generator().manual_seed(1)
+    pages = (torch.randperm(T // P, generator=g) + 1).to(dev)
+    slot = (pages[pos.long() // P] * P + pos.long() % P).int()
+    slot_l = slot.long()
+    kpool = torch.zeros(T // P + 1, P, Hkv, D, device=dev,
+                        dtype=torch.bfloat16)
+    vpool = torch.zeros_like(kpool)
+    kflat, vflat = kpool.view(-1, Hkv, D), vpool.view(-1, Hkv, D)
+
+    def fused():
+        return hip.paged_prefill_rope_cache(qkv, kpool, vpool, cos, sin, pos,
+                                            slot)
+
+    def unfused():
+        q, k, v = qkv.split([Hq * D, Hkv * D, Hkv * D], dim=-1)
+        q = ops.rope(q.reshape(1, T, Hq, D).contiguous(), cos, sin)
+        k = ops.rope(k.reshape(1, T, Hkv, D).contiguous(), cos, sin)
+        v = v.reshape(1, T, Hkv, D).contiguous()
+        kflat.index_copy_(0, slot_l, k[0])
+        vflat.index_copy_(0, slot_l, v[0])
+        return q
+
+    qf = fused()
+    kf = kpool.clone()
+    same = torch.equal(qf, unfused()[0]) and torch.equal(kf, kpool)
+    res = _alternate({"fused": fused, "unfused": unfused}, iters * 20, rounds)
+    _show(f"rope + page append T{T} H{Hq}/{Hkv} P{P} bit-identical {same}",
+          res, "unfused")
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--B", type=int, default=4)
@@ -104,10 +227,15 @@ def main():
     p.add_argument("--Hkv", type=int, default=8)
     p.add_argument("--iters", type=int, default=20)
     p.add_argument("--mode", type=str, default="both",
-                   choices=["fwd", "bwd", "both", "paged-prefill"],
+                   choices=["fwd", "bwd", "both", "paged-prefill",
+                            "paged-prefill-ragged"],
                    help="paged-prefill: time paged_prefill_attn at ctx=0 "
                         "against attn_fwd (fixed shapes B4 S4096 and "
-                        "B1 S512, H32/8, page sizes 16 and 64)")
+                        "B1 S512, H32/8, page sizes 16 and 64); "
+                        "paged-prefill-ragged: time the ragged kernel "
+                        "against paged_prefill_attn at equal and mixed "
+                        "lengths, and the fused rope + page append against "
+                        "the dispatches it replaces")
     p.add_argument("--dq-mode", type=str, default=None,
                    choices=["stream", "recompute"],
                    help="dQ path of the backward (default: the extension's "
@@ -120,6 +248,9 @@ def main():
     args = p.parse_args()
     if args.mode == "paged-prefill":
         bench_paged_prefill(args.iters)
+        return
+    if args.mode == "paged-prefill-ragged":
+        bench_paged_prefill_ragged(args.iters)
         return
     B, S, Hq, Hkv, D = args.B, args.S, args.Hq, args.Hkv, 128
     if args.dkv_impl is not None:

@@ -17,6 +17,8 @@ B * S * 8 heads * 128 * 2 (k+v) * 2 bytes = 8 KB per token-row
 
 from __future__ import annotations
 
+import itertools
+from collections import ChainMap
 from dataclasses import dataclass
 from typing import Optional
 
@@ -246,6 +248,96 @@ def prefill_extend(model: LlamaModel, tokens: torch.Tensor, caches: list,
         x = x + blk.wdown(ops.swiglu_packed(blk.wgu(xn)))
     x = ops.rmsnorm(x, model.final_norm, cfg.rms_eps)
     return model.lm_head(x[:, -1])
+
+
+@dataclass
+class RaggedPass:
+    """What one ragged prefill pass works out once and every layer reuses:
+    per packed token its logical position and physical pool row, per
+    sequence its cached length and block-table row, the attention launch
+    plan, and the packed index of each sequence's last token."""
+    q_lens: list
+    pos: torch.Tensor    # int32 [T]
+    slot: torch.Tensor   # int32 [T]
+    ctx: torch.Tensor    # int32 [B]
+    table: torch.Tensor  # int32 [B, M]
+    plan: "ops.RaggedPlan"
+    last: torch.Tensor   # int64 [B]
+
+    @staticmethod
+    def build(model, caches: list, rows, q_lens, ctx,
+              device: torch.device) -> "RaggedPass":
+        q_lens = [int(n) for n in q_lens]
+        ctx = [int(c) for c in ctx]
+        assert len(rows) == len(q_lens) == len(ctx) >= 1
+        assert min(q_lens) >= 1 and min(ctx) >= 0
+        cache = caches[0]
+        assert isinstance(cache, PagedKVCache), "paged caches only"
+        P = cache.page_size
+        ends = [c + n for c, n in zip(ctx, q_lens)]
+        assert max(ends) <= model.rope_cos.shape[0], "beyond the rope tables"
+        assert max(ends) <= cache.block_table.shape[1] * P, \
+            "beyond the block table"
+        # host lists -> one small copy each, no device sync
+        seq = [b for b, n in enumerate(q_lens) for _ in range(n)]
+        pos = [c + i for c, n in zip(ctx, q_lens) for i in range(n)]
+        plan = ops.RaggedPlan(q_lens, device, ctx=ctx)
+
+        def dev(v, dtype):
+            return torch.tensor(v, dtype=dtype, device=device)
+
+        table = cache.block_table[dev(list(rows), torch.long)]
+        pos_l = dev(pos, torch.long)
+        slot = table[dev(seq, torch.long), pos_l // P].long() * P + pos_l % P
+        return RaggedPass(q_lens, pos_l.int(), slot.int(),
+                          dev(ctx, torch.int32), table.contiguous(), plan,
+                          dev([e - 1 for e in plan.cu[1:]], torch.long))
+
+
+def _ragged_attention(model, blk, cache: PagedKVCache, x: torch.Tensor,
+                      rp: RaggedPass) -> torch.Tensor:
+    """Attention half of a block over packed tokens x [1, T, H]: rope and
+    page append in one dispatch, ragged attention over the block table."""
+    cfg = model.cfg
+    assert isinstance(cache, PagedKVCache), "paged caches only"
+    T = x.shape[1]
+    xn = ops.rmsnorm(x, blk.attn_norm, cfg.rms_eps)
+    q = ops.paged_prefill_rope_cache(
+        blk.wqkv(xn).reshape(T, -1), cache.kpool, cache.vpool,
+        model.rope_cos, model.rope_sin, rp.pos, rp.slot, cfg.num_heads)
+    attn = ops.paged_prefill_attention_ragged(
+        q, cache.kpool, cache.vpool, rp.table, rp.q_lens, rp.ctx,
+        plan=rp.plan)
+    return x + blk.wo(attn.reshape(1, T, cfg.q_dim))
+
+
+def _ragged_logits(model, x: torch.Tensor, rp: RaggedPass) -> torch.Tensor:
+    x = ops.rmsnorm(x[:, rp.last], model.final_norm, model.cfg.rms_eps)
+    return model.lm_head(x)[0]
+
+
+@torch.no_grad()
+def prefill_ragged(model: LlamaModel, tokens: torch.Tensor, caches: list,
+                   rows, q_lens, ctx) -> torch.Tensor:
+    """``prefill_extend`` for several sequences of different lengths in
+    ONE pass. tokens [T] holds the chunks packed back to back: sequence b
+    contributes ``q_lens[b]`` tokens at positions ``ctx[b] ..`` behind the
+    ``ctx[b]`` rows the paged caches already hold for it, and uses
+    block-table row ``rows[b]`` (``caches`` are the whole-batch caches).
+    ``q_lens`` and ``ctx`` are host lists. The per-token ops see a
+    [1, T] batch; ``ops.paged_prefill_rope_cache`` appends every token's
+    K/V before ``ops.paged_prefill_attention_ragged`` runs, so a sequence
+    may read pages another sequence of the same pass fills. Returns the
+    logits of each sequence's last token, [B, vocab]."""
+    cfg = model.cfg
+    rp = RaggedPass.build(model, caches, rows, q_lens, ctx, tokens.device)
+    assert tokens.dim() == 1 and tokens.numel() == rp.plan.T
+    x = model.embed(tokens[None])
+    for blk, cache in zip(model.blocks, caches):
+        x = _ragged_attention(model, blk, cache, x, rp)
+        xn = ops.rmsnorm(x, blk.mlp_norm, cfg.rms_eps)
+        x = x + blk.wdown(ops.swiglu_packed(blk.wgu(xn)))
+    return _ragged_logits(model, x, rp)
 
 
 @torch.no_grad()
@@ -535,17 +627,25 @@ class PagedBatcher:
     holder frees it; a holder of a child page always holds the parent, so
     no stale chain survives a page's reuse. With both options off,
     ``admit`` is the whole-prompt dense-kernel path.
+
+    ``admit_many`` admits several requests in one call and prefills them
+    together, packed, through ``ragged_fn`` (default ``prefill_ragged``;
+    pass ``generate_moe.prefill_ragged_moe`` for Mixtral); it honours
+    both options above and leaves the same state as one ``admit`` per
+    request.
     """
 
     def __init__(self, model, max_batch: int, max_len: int, num_pages: int,
                  page_size: int = 16, prefill_fn=None, decode_fn=None,
                  prefix_sharing: bool = False,
-                 prefill_chunk: Optional[int] = None, extend_fn=None):
+                 prefill_chunk: Optional[int] = None, extend_fn=None,
+                 ragged_fn=None):
         self.model = model
         self.cfg = model.cfg
         self._prefill = prefill_fn or prefill
         self._decode = decode_fn or decode_step
         self._extend = extend_fn or prefill_extend
+        self._ragged = ragged_fn or prefill_ragged
         assert prefill_chunk is None or prefill_chunk >= 1
         self.prefix_sharing = prefix_sharing
         self.prefill_chunk = prefill_chunk
@@ -658,6 +758,138 @@ class PagedBatcher:
         self.pos_host[row] = S0
         self.active[row] = True
         return nxt[0]
+
+    def _count_fresh_pages(self, prompts_toks: list) -> int:
+        """Dry run of ``admit_many``'s allocation: the pages the prompts
+        need beyond the ones they can map, with prompt j also mapping the
+        full pages an earlier prompt of the same call will fill (those
+        stand in as negative ids). Changes nothing."""
+        # the real placement, over a copy-on-write view of the index and
+        # with stand-in page ids (-1 is the root parent)
+        staged = ChainMap({}, self._index)
+        ids = itertools.count(-2, -1)
+        taken = 0
+
+        def stand_ins(n):
+            nonlocal taken
+            taken += n
+            return [next(ids) for _ in range(n)]
+
+        for toks in prompts_toks:
+            self._place_prompt(toks, staged, {}, stand_ins)
+        return taken
+
+    def _place_prompt(self, toks: list, index, page_key, alloc):
+        """Pages for one prompt, as ``admit`` chooses them: map the
+        indexed chain over its full pages (at most ``(S0 - 1) // P``, so
+        one token is computed), take the rest from ``alloc(n)``, then
+        register its own full prompt pages in ``index`` / ``page_key``,
+        stopping at a key another row's page already holds. Returns
+        (mapped pages, all pages)."""
+        P = self.page_size
+        S0 = len(toks)
+        hits = []
+        if self.prefix_sharing:
+            parent = -1
+            for j in range((S0 - 1) // P):
+                page = index.get((parent, tuple(toks[j * P:(j + 1) * P])))
+                if page is None:
+                    break
+                hits.append(page)
+                parent = page
+        pages = hits + alloc(-(-(S0 + 1) // P) - len(hits))
+        if self.prefix_sharing:
+            parent = -1
+            for j in range(S0 // P):
+                key = (parent, tuple(toks[j * P:(j + 1) * P]))
+                if index.setdefault(key, pages[j]) != pages[j]:
+                    break
+                page_key[pages[j]] = key
+                parent = pages[j]
+        return hits, pages
+
+    @torch.no_grad()
+    def admit_many(self, rows, prompts) -> torch.Tensor:
+        """``admit`` for several requests at once: prompt i goes to batch
+        row ``rows[i]``, and all of them are prefilled together through
+        ``ragged_fn`` (packed, each behind its own cached prefix) instead
+        of one pass per request. Returns the first generated tokens [n],
+        in call order. Raises OutOfPages, with no state changed, unless
+        the pool can hold every prompt plus its first decode position.
+
+        With ``prefix_sharing`` the prompts walk and join the index in
+        call order, exactly as sequential ``admit`` calls would, so prompt
+        j also maps the full pages that prompt i < j of the same call
+        fills: every layer appends the K/V of all packed tokens before
+        its attention runs. ``prefill_chunk=N`` is a token budget per
+        pass: the prompts are packed greedily in call order and split
+        across passes where needed, so every token of i is in the same
+        or an earlier pass than any token of j > i."""
+        rows = [int(r) for r in rows]
+        assert len(rows) == len(prompts) >= 1
+        assert len(set(rows)) == len(rows), "rows must be distinct"
+        P = self.page_size
+        toks = [p.reshape(-1).tolist() for p in prompts]
+        for row, t in zip(rows, toks):
+            assert not self.active[row], f"row {row} is occupied"
+            assert 1 <= len(t) and len(t) + 1 < self.max_len
+        # all-or-nothing over the whole call, before anything changes
+        need = self._count_fresh_pages(toks)
+        if need > self.allocator.num_free:
+            raise OutOfPages(
+                f"need {need} pages, {self.allocator.num_free} free")
+        table = torch.zeros(len(rows), self.table_width, dtype=torch.int32)
+        starts = []
+        for i, (row, t) in enumerate(zip(rows, toks)):
+            hits, pages = self._place_prompt(t, self._index, self._page_key,
+                                             self.allocator.alloc)
+            self.allocator.share(hits)
+            self.pages[row] = pages
+            table[i, :len(pages)] = torch.tensor(pages, dtype=torch.int32)
+            self.shared_tokens[row] = len(hits) * P
+            starts.append(len(hits) * P)
+        rows_dev = torch.tensor(rows, dtype=torch.long, device=self.device)
+        self.block_table[rows_dev] = table.to(self.device)
+
+        # greedy packing in call order under the per-pass token budget
+        budget = self.prefill_chunk or sum(len(t) for t in toks)
+        passes, cur, room = [], [], budget
+        for i, t in enumerate(toks):
+            c = starts[i]
+            while c < len(t):
+                n = min(room, len(t) - c)
+                cur.append((i, c, n))
+                c += n
+                room -= n
+                if room == 0:
+                    passes.append(cur)
+                    cur, room = [], budget
+        if cur:
+            passes.append(cur)
+        prompts_dev = [p.reshape(-1).to(self.device) for p in prompts]
+        first = torch.zeros(len(rows), dtype=torch.long, device=self.device)
+        for chunk in passes:
+            logits = self._ragged(
+                self.model,
+                torch.cat([prompts_dev[i][c:c + n] for i, c, n in chunk]),
+                self.caches, [rows[i] for i, _, _ in chunk],
+                [n for _, _, n in chunk], [c for _, c, _ in chunk])
+            # sequences whose prompt ends in this pass
+            done = [(k, i) for k, (i, c, n) in enumerate(chunk)
+                    if c + n == len(toks[i])]
+            if done:
+                k_dev = torch.tensor([k for k, _ in done], device=self.device)
+                i_dev = torch.tensor([i for _, i in done], device=self.device)
+                first[i_dev] = logits[k_dev].argmax(-1)
+        lens = [len(t) for t in toks]
+        self.tok[rows_dev, 0] = first
+        self.pos[rows_dev] = torch.tensor(lens, dtype=torch.int32,
+                                          device=self.device)
+        self.mask[rows_dev] = 1
+        for row, S0 in zip(rows, lens):
+            self.pos_host[row] = S0
+            self.active[row] = True
+        return first
 
     def retire(self, row: int) -> None:
         """Free the row's pages and park it on the dump page."""

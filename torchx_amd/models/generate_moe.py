@@ -23,10 +23,13 @@ import torch
 
 from torchx_amd import ops
 
-from .generate import KVCache, PagedKVCache
+from .generate import (
+    KVCache, PagedKVCache, RaggedPass, _ragged_attention, _ragged_logits,
+)
 from .mixtral import MixtralModel, MoELayer
 
-__all__ = ["prefill_moe", "prefill_extend_moe", "decode_step_moe", "generate_moe", "KVCache"]
+__all__ = ["prefill_moe", "prefill_extend_moe", "prefill_ragged_moe",
+           "decode_step_moe", "generate_moe", "KVCache"]
 
 
 def _moe_mlp_decode(moe: MoELayer, x: torch.Tensor) -> torch.Tensor:
@@ -119,6 +122,24 @@ def prefill_extend_moe(model: MixtralModel, tokens: torch.Tensor,
         x = x + blk.moe(xn)
     x = ops.rmsnorm(x, model.final_norm, cfg.rms_eps)
     return model.lm_head(x[:, -1])
+
+
+@torch.no_grad()
+def prefill_ragged_moe(model: MixtralModel, tokens: torch.Tensor,
+                       caches: list, rows, q_lens, ctx) -> torch.Tensor:
+    """generate.prefill_ragged with the MoE MLP: tokens [T] packed from
+    several sequences, sequence b with ``q_lens[b]`` tokens behind
+    ``ctx[b]`` cached rows of block-table row ``rows[b]``; returns each
+    sequence's last-token logits [B, vocab]."""
+    cfg = model.cfg
+    rp = RaggedPass.build(model, caches, rows, q_lens, ctx, tokens.device)
+    assert tokens.dim() == 1 and tokens.numel() == rp.plan.T
+    x = model.embed(tokens[None])
+    for blk, cache in zip(model.blocks, caches):
+        x = _ragged_attention(model, blk, cache, x, rp)
+        xn = ops.rmsnorm(x, blk.mlp_norm, cfg.rms_eps)
+        x = x + blk.moe(xn)
+    return _ragged_logits(model, x, rp)
 
 
 @torch.no_grad()

@@ -662,6 +662,115 @@ def paged_prefill_attention(q: torch.Tensor, kpool: torch.Tensor,
     return torch.cat(outs, dim=0)
 
 
+class RaggedPlan:
+    """Host-side launch plan of ``paged_prefill_attention_ragged`` for one
+    packing: ``q_lens`` (chunk length per sequence), ``cu`` (first packed
+    row per sequence, plus the total ``T``) and the device tile list
+    int32 [ntiles, 4] = (sequence, q tile, cu, chunk length), one entry per
+    128-row q tile. Everything comes from host lengths, so building a plan
+    never waits on the device; build it once per forward pass and hand it
+    to every layer (one host-to-device copy in all).
+
+    ``heavy_first`` lists the tiles by falling number of keys they attend
+    (``ctx[b] + 128 * (qt + 1)``, from the host ``ctx`` if given), so the
+    longest-running blocks are dispatched first; otherwise tiles are
+    listed sequence by sequence."""
+
+    HEAVY_FIRST = True
+
+    def __init__(self, q_lens, device, ctx=None,
+                 heavy_first: Optional[bool] = None):
+        self.q_lens = [int(n) for n in q_lens]
+        assert self.q_lens and min(self.q_lens) >= 1, "q_lens must be >= 1"
+        self.cu = [0]
+        for n in self.q_lens:
+            self.cu.append(self.cu[-1] + n)
+        self.T = self.cu[-1]
+        ctx = [0] * len(self.q_lens) if ctx is None else [int(c) for c in ctx]
+        assert len(ctx) == len(self.q_lens)
+        tiles = [(b, qt, self.cu[b], n)
+                 for b, n in enumerate(self.q_lens)
+                 for qt in range(-(-n // 128))]
+        if heavy_first is None:
+            heavy_first = self.HEAVY_FIRST
+        if heavy_first:
+            # stable: equal costs keep the sequence order
+            tiles.sort(key=lambda t: -(ctx[t[0]] + min(128 * (t[1] + 1),
+                                                       t[3])))
+        self.tiles_host = tiles
+        self.tiles = torch.tensor(tiles, dtype=torch.int32, device=device)
+
+
+def paged_prefill_attention_ragged(q: torch.Tensor, kpool: torch.Tensor,
+                                   vpool: torch.Tensor,
+                                   block_table: torch.Tensor, q_lens,
+                                   ctx: torch.Tensor,
+                                   scale: Optional[float] = None,
+                                   plan: Optional[RaggedPlan] = None
+                                   ) -> torch.Tensor:
+    """``paged_prefill_attention`` over chunks of different lengths. q
+    [T, Hq, D] holds the query rows of B sequences packed back to back:
+    sequence b owns rows ``cu[b] .. cu[b]+q_lens[b]-1`` at logical
+    positions ``ctx[b] ..``; the pools already hold its
+    ``ctx[b] + q_lens[b]`` rows through ``block_table[b]``. ``q_lens`` is a
+    host sequence of ints >= 1 summing to T, ``ctx`` int32 [B] on the
+    device. Row i of sequence b attends t <= ctx[b] + i -> o [T, Hq, D].
+    On the GPU (D = 128) sequence b's rows are bit-identical to
+    ``paged_prefill_attention`` on that sequence alone, at every ctx.
+    ``plan`` is the ``RaggedPlan`` of ``q_lens``; pass one plan to all
+    layers of a forward pass (without it one is built per call)."""
+    if scale is None:
+        scale = 1.0 / math.sqrt(q.shape[-1])
+    if plan is None:
+        plan = RaggedPlan(q_lens, q.device)
+    assert plan.q_lens == [int(n) for n in q_lens], "plan of other lengths"
+    assert q.dim() == 3 and q.shape[0] == plan.T, (q.shape, plan.T)
+    assert block_table.shape[0] == len(plan.q_lens) == ctx.numel()
+    if _on_gpu(q):
+        return hip_ops().paged_prefill_attn_ragged(
+            q.contiguous(), kpool, vpool, block_table.contiguous(),
+            ctx.contiguous(), plan.tiles, scale)
+    outs = []
+    for b, n in enumerate(plan.q_lens):
+        c = int(ctx[b].item())
+        qb = q[plan.cu[b]:plan.cu[b] + n][None]
+        outs.append(reference.attention_prefix(
+            qb, reference.paged_gather(kpool, block_table[b], c + n),
+            reference.paged_gather(vpool, block_table[b], c + n), c,
+            scale)[0])
+    return torch.cat(outs, dim=0)
+
+
+def paged_prefill_rope_cache(qkv: torch.Tensor, kpool: torch.Tensor,
+                             vpool: torch.Tensor, cos: torch.Tensor,
+                             sin: torch.Tensor, pos: torch.Tensor,
+                             slot: torch.Tensor,
+                             num_heads: int) -> torch.Tensor:
+    """Fused rope + page append for a packed prefill: qkv
+    [T, (Hq+2*Hkv)*D] is the wqkv output of T tokens, token t at logical
+    position ``pos[t]``. Returns the roped q [T, Hq, D] (contiguous) and
+    writes the roped k and the raw v of token t to physical pool row
+    ``slot[t]`` (= page * P + pos % P). cos/sin are the FULL f32 [S, D/2]
+    tables; ``pos`` and ``slot`` are int32 [T], computed once per forward
+    pass. Bit-identical to ``rope`` + ``PagedKVCache.store_rows``."""
+    T = qkv.shape[0]
+    Hkv, D = kpool.shape[2], kpool.shape[3]
+    if _on_gpu(qkv):
+        return hip_ops().paged_prefill_rope_cache(
+            qkv.contiguous(), kpool, vpool, cos, sin, pos.contiguous(),
+            slot.contiguous())
+    q, k, v = qkv.split([num_heads * D, Hkv * D, Hkv * D], dim=-1)
+    p = pos.long()
+    # rope takes [B, S, H, D] with cos/sin [S, D/2]: one batch of T rows
+    cs, sn = cos[p], sin[p]
+    q = rope(q.reshape(1, T, num_heads, D).contiguous(), cs, sn)[0]
+    k = rope(k.reshape(1, T, Hkv, D).contiguous(), cs, sn)[0]
+    kpool.view(-1, Hkv, D).index_copy_(0, slot.long(), k)
+    vpool.view(-1, Hkv, D).index_copy_(0, slot.long(),
+                                       v.reshape(T, Hkv, D).contiguous())
+    return q.contiguous()
+
+
 def paged_decode_rope_cache(qkv: torch.Tensor, kpool: torch.Tensor,
                             vpool: torch.Tensor, block_table: torch.Tensor,
                             cos: torch.Tensor, sin: torch.Tensor,

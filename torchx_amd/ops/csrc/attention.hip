@@ -25,7 +25,9 @@
 //  * Forward block size is 4 waves at every length (the 8-wave variant
 //    stays selectable for re-measurement, see attn_fwd_launch).
 //  * paged_prefill_attn_kernel: the 4-wave forward over a block-table KV
-//    cache, for a chunk of query rows behind an already cached prefix.
+//    cache, for a chunk of query rows behind an already cached prefix;
+//    paged_prefill_attn_ragged_kernel: the same block work over a packed
+//    batch of chunks of different lengths (host-built tile list).
 //  * Backward is FA2-style without atomics: preprocess delta =
 //    rowsum(dO*O); ONE dK+dV kernel, 4 waves at one wave per SIMD, in
 //    which a wave accumulates both dK and dV for its 32 kv rows (S, P and
@@ -572,23 +574,19 @@ __device__ __forceinline__ void stage_paged_glds(
   }
 }
 
-__global__ void __launch_bounds__(256, 2)
-paged_prefill_attn_kernel(const unsigned short* __restrict__ q,
-                          const unsigned short* __restrict__ kpool,
-                          const unsigned short* __restrict__ vpool,
-                          unsigned short* __restrict__ o,
-                          const int* __restrict__ bt,   // [B, M]
-                          const int* __restrict__ ctx,  // [B]
-                          int B, int S, int Hq, int Hkv, int num_pages,
-                          int logP, int M, float scale) {
-  __shared__ __align__(16) char smem[4 * KIMG_BYTES];
-
+// One block's work, shared by the [B, S] kernel and the ragged one: q tile
+// `qt` (128 rows) of one (sequence, q head). `qb` / `ob` point at the
+// sequence's first chunk row of that head, `kb` / `vb` at the kv head's
+// column of pool row 0, `bt_row` at the sequence's table row; the chunk
+// has S rows behind `ctx_b` cached ones. All four waves run every barrier.
+__device__ __forceinline__ void paged_prefill_tile(
+    const unsigned short* __restrict__ qb,
+    const unsigned short* __restrict__ kb,
+    const unsigned short* __restrict__ vb,
+    unsigned short* __restrict__ ob,
+    const int* __restrict__ bt_row, int ctx_b, int S, int qt, int Hq,
+    int Hkv, int num_pages, int logP, int M, float scale, char* smem) {
   const int BQ = 4 * QBLK;
-  const int nqt = (S + BQ - 1) / BQ;
-  const int G = Hq / Hkv;
-  int b, hq, qt;
-  map_block_fwd(B, Hq, Hkv, nqt, G, &b, &hq, &qt);
-  const int hkv = hq / G;
 
   const int wave = threadIdx.x / 64;
   const int lane = threadIdx.x & 63;
@@ -598,16 +596,12 @@ paged_prefill_attn_kernel(const unsigned short* __restrict__ q,
   // cached rows before the chunk, and the sequence length; compare before
   // adding so a garbage ctx cannot overflow
   const int cap = M << logP;
-  const int c0 = min(max(ctx[b], 0), cap);
+  const int c0 = min(max(ctx_b, 0), cap);
   const int L = (S > cap - c0) ? cap : c0 + S;
   const int pmask = (1 << logP) - 1;
-  const int* bt_row = bt + (long)b * M;
 
   const long q_seq_stride = (long)Hq * HD;
   const long kv_seq_stride = (long)Hkv * HD;
-  const unsigned short* qb = q + (long)b * S * q_seq_stride + (long)hq * HD;
-  const unsigned short* kb = kpool + (long)hkv * HD;
-  const unsigned short* vb = vpool + (long)hkv * HD;
 
   const int q0_blk = qt * BQ;
   const int qw0 = q0_blk + wave * QBLK;       // wave's first q row
@@ -753,7 +747,7 @@ paged_prefill_attn_kernel(const unsigned short* __restrict__ q,
   if (!wave_active || q_row >= S) return;
 
   const float inv_l = (l_run > 0.f) ? 1.0f / l_run : 0.f;
-  unsigned short* ob = o + (((long)b * S + q_row) * Hq + hq) * HD;
+  unsigned short* orow = ob + q_row * q_seq_stride;
   #pragma unroll
   for (int dt = 0; dt < 4; ++dt) {
     #pragma unroll
@@ -764,9 +758,92 @@ paged_prefill_attn_kernel(const unsigned short* __restrict__ q,
       for (int j = 0; j < 4; ++j) {
         w[j] = (short)f32_to_bf16(acc_o[dt][4 * g + j] * inv_l);
       }
-      *(bf16x4_raw*)(ob + dt * 32 + 8 * g + 4 * (hi ? 1 : 0)) = w;
+      *(bf16x4_raw*)(orow + dt * 32 + 8 * g + 4 * (hi ? 1 : 0)) = w;
     }
   }
+}
+
+__global__ void __launch_bounds__(256, 2)
+paged_prefill_attn_kernel(const unsigned short* __restrict__ q,
+                          const unsigned short* __restrict__ kpool,
+                          const unsigned short* __restrict__ vpool,
+                          unsigned short* __restrict__ o,
+                          const int* __restrict__ bt,   // [B, M]
+                          const int* __restrict__ ctx,  // [B]
+                          int B, int S, int Hq, int Hkv, int num_pages,
+                          int logP, int M, float scale) {
+  __shared__ __align__(16) char smem[4 * KIMG_BYTES];
+
+  const int nqt = (S + 4 * QBLK - 1) / (4 * QBLK);
+  const int G = Hq / Hkv;
+  int b, hq, qt;
+  map_block_fwd(B, Hq, Hkv, nqt, G, &b, &hq, &qt);
+  const int hkv = hq / G;
+  const long seq_off = ((long)b * S * Hq + hq) * HD;
+  paged_prefill_tile(q + seq_off, kpool + (long)hkv * HD,
+                     vpool + (long)hkv * HD, o + seq_off, bt + (long)b * M,
+                     ctx[b], S, qt, Hq, Hkv, num_pages, logP, M, scale, smem);
+}
+
+// ---------------------------------------------------------------------------
+// Ragged paged prefill: the same block work over a PACKED q [T, Hq, 128]
+// holding the chunks of B sequences of different lengths back to back.
+//
+//   tiles  int4 [ntiles], built on the host from the lengths: (sequence b,
+//          q tile qt of that sequence, cu[b] = its first packed row, S_b =
+//          its chunk length). Tile qt of sequence b covers packed rows
+//          cu[b] + 128*qt .. +127, cut at S_b: a tile never holds rows of
+//          two sequences.
+//   bt     int32 [B, M], ctx int32 [B]: row b is sequence b's.
+//
+// A block is paged_prefill_tile on (q + cu[b] rows, S_b, ctx[b], qt), the
+// very call the [B, S] kernel makes for a batch holding sequence b alone,
+// so sequence b's output is bit-identical to that kernel's at every ctx.
+//
+// Block map. A unit is a (tile, kv head) pair, unit = tile * Hkv + hkv,
+// and owns G = Hq / Hkv blocks, one per q head of the group. The
+// dispatcher deals consecutive blockIdx to consecutive XCDs, so with
+// xcd = bid & 7, slot = bid >> 3 the blocks of unit (slot / G) * 8 + xcd
+// all sit on one XCD and read its K/V stream through one L2. The grid is
+// rounded up to whole rounds of 8 units; blocks of a unit past the end
+// leave as a whole before any barrier. With Hkv % 8 == 0 every tile of a
+// (sequence, kv head) lands on XCD hkv & 7, as in map_block_fwd; with a
+// smaller Hkv the tiles of one stream spread over 8 / Hkv XCDs (no equal
+// group size exists to deal whole streams to XCDs when lengths differ).
+// Units are walked in tile-list order, which the host chooses.
+//
+// Tile contents are clamped (b to [0, B), cu to [0, T), S_b to
+// [1, T - cu], qt to a tile of the chunk), so no list can address outside
+// q, o or the table; the pools are guarded as in the [B, S] kernel.
+// ---------------------------------------------------------------------------
+__global__ void __launch_bounds__(256, 2)
+paged_prefill_attn_ragged_kernel(
+    const unsigned short* __restrict__ q,      // [T, Hq, 128]
+    const unsigned short* __restrict__ kpool,
+    const unsigned short* __restrict__ vpool,
+    unsigned short* __restrict__ o,            // [T, Hq, 128]
+    const int* __restrict__ bt,                // [B, M]
+    const int* __restrict__ ctx,               // [B]
+    const int4* __restrict__ tiles,            // [ntiles]
+    int ntiles, int B, int T, int Hq, int Hkv, int num_pages, int logP,
+    int M, float scale) {
+  __shared__ __align__(16) char smem[4 * KIMG_BYTES];
+
+  const int G = Hq / Hkv;
+  const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
+  const int unit = (slot / G) * 8 + xcd;
+  if (unit >= ntiles * Hkv) return;  // block-uniform: the padding units
+  const int hkv = unit % Hkv;
+  const int hq = hkv * G + slot % G;
+  const int4 td = tiles[unit / Hkv];
+  const int b = min(max(td.x, 0), B - 1);
+  const int cu = min(max(td.z, 0), T - 1);
+  const int S = min(max(td.w, 1), T - cu);
+  const int qt = min(max(td.y, 0), (S - 1) / (4 * QBLK));
+  const long seq_off = ((long)cu * Hq + hq) * HD;
+  paged_prefill_tile(q + seq_off, kpool + (long)hkv * HD,
+                     vpool + (long)hkv * HD, o + seq_off, bt + (long)b * M,
+                     ctx[b], S, qt, Hq, Hkv, num_pages, logP, M, scale, smem);
 }
 
 // ---------------------------------------------------------------------------
@@ -2012,6 +2089,22 @@ extern "C" void paged_prefill_attn_launch(
                      (const unsigned short*)vpool, (unsigned short*)o,
                      (const int*)bt, (const int*)ctx, B, S, Hq, Hkv,
                      num_pages, logP, M, scale);
+}
+
+extern "C" void paged_prefill_attn_ragged_launch(
+    const void* q, const void* kpool, const void* vpool, void* o,
+    const void* bt, const void* ctx, const void* tiles, int ntiles, int B,
+    int T, int Hq, int Hkv, int num_pages, int logP, int M, float scale,
+    hipStream_t stream) {
+  // whole rounds of 8 units, G blocks each (see the kernel's block map)
+  const long units = (long)ntiles * Hkv;
+  const long grid = (units + 7) / 8 * 8 * (Hq / Hkv);
+  hipLaunchKernelGGL(paged_prefill_attn_ragged_kernel, dim3((unsigned)grid),
+                     dim3(256), 0, stream, (const unsigned short*)q,
+                     (const unsigned short*)kpool,
+                     (const unsigned short*)vpool, (unsigned short*)o,
+                     (const int*)bt, (const int*)ctx, (const int4*)tiles,
+                     ntiles, B, T, Hq, Hkv, num_pages, logP, M, scale);
 }
 
 // dK/dV implementation of the backward: 1 = merged (one wave accumulates

@@ -68,6 +68,14 @@ void paged_decode_rope_cache_launch(const void*, void*, void*, void*,
 void paged_prefill_attn_launch(const void*, const void*, const void*, void*,
                                const void*, const void*, int, int, int, int,
                                int, int, int, float, hipStream_t);
+void paged_prefill_attn_ragged_launch(const void*, const void*, const void*,
+                                      void*, const void*, const void*,
+                                      const void*, int, int, int, int, int,
+                                      int, int, int, float, hipStream_t);
+void paged_prefill_rope_cache_launch(const void*, void*, void*, void*,
+                                     const void*, const void*, const void*,
+                                     const void*, long, int, int, long, int,
+                                     hipStream_t);
 }
 
 namespace {
@@ -673,6 +681,81 @@ at::Tensor paged_prefill_attn(at::Tensor q, at::Tensor kpool,
   return o;
 }
 
+// q [T, Hq, 128]: the chunks of B sequences packed back to back. tiles is
+// the host-built int32 [ntiles, 4] list (sequence, q tile, first packed
+// row, chunk length); the kernel clamps every field, so its content cannot
+// address outside q, o or the table. Returns o [T, Hq, 128].
+at::Tensor paged_prefill_attn_ragged(at::Tensor q, at::Tensor kpool,
+                                     at::Tensor vpool, at::Tensor bt,
+                                     at::Tensor ctx, at::Tensor tiles,
+                                     double scale) {
+  check_bf16(q, "q");
+  TORCH_CHECK(q.dim() == 3 && q.size(2) == 128, "q must be [T, Hq, 128]");
+  TORCH_CHECK(q.size(0) >= 1 && q.size(0) < (1L << 30), "need 1 <= T < 2^30");
+  const int T = q.size(0), Hq = q.size(1);
+  const int B = bt.dim() == 2 ? bt.size(0) : 0;
+  const int logP = check_paged(kpool, vpool, bt, ctx, B);
+  TORCH_CHECK(B >= 1 && ctx.dim() == 1, "ctx must be int32 [B], B >= 1");
+  TORCH_CHECK(tiles.is_cuda() && tiles.scalar_type() == at::kInt &&
+                  tiles.dim() == 2 && tiles.size(1) == 4 &&
+                  tiles.size(0) >= 1 && tiles.is_contiguous(),
+              "tiles must be a contiguous int32 [ntiles, 4] device tensor");
+  const int num_pages = kpool.size(0), Hkv = kpool.size(2);
+  const int M = bt.size(1);
+  TORCH_CHECK(Hq % Hkv == 0, "GQA group mismatch");
+  const long ntiles = tiles.size(0);
+  TORCH_CHECK((ntiles * Hkv + 7) / 8 * 8 * (Hq / Hkv) < (1L << 31),
+              "grid too large");
+  auto o = at::empty_like(q);
+  paged_prefill_attn_ragged_launch(
+      q.data_ptr(), kpool.data_ptr(), vpool.data_ptr(), o.data_ptr(),
+      bt.data_ptr(), ctx.data_ptr(), tiles.data_ptr(), (int)ntiles, B, T, Hq,
+      Hkv, num_pages, logP, M, (float)scale, cur_stream());
+  return o;
+}
+
+// qkv [T, (Hq+2*Hkv)*128], packed tokens: ropes q/k of token t at pos[t],
+// writes k/v to pool row slot[t], returns q [T, Hq, 128].
+at::Tensor paged_prefill_rope_cache(at::Tensor qkv, at::Tensor kpool,
+                                    at::Tensor vpool, at::Tensor cos_t,
+                                    at::Tensor sin_t, at::Tensor pos,
+                                    at::Tensor slot) {
+  check_bf16(qkv, "qkv");
+  check_bf16(kpool, "kpool");
+  check_bf16(vpool, "vpool");
+  check_f32(cos_t, "cos");
+  check_f32(sin_t, "sin");
+  TORCH_CHECK(qkv.dim() == 2 && qkv.size(0) >= 1,
+              "qkv must be [T, (Hq+2*Hkv)*128]");
+  TORCH_CHECK(kpool.dim() == 4 && kpool.sizes() == vpool.sizes() &&
+                  kpool.size(3) == 128 && kpool.size(0) >= 1 &&
+                  kpool.size(1) >= 1 && kpool.size(2) >= 1,
+              "kpool/vpool must be [num_pages, P, Hkv, 128], same shape");
+  const long T = qkv.size(0);
+  const int Hkv = kpool.size(2);
+  const long pool_rows = kpool.size(0) * kpool.size(1);
+  TORCH_CHECK(pool_rows < (1L << 31), "pool too large for int32 slots");
+  for (const at::Tensor* t : {&pos, &slot}) {
+    TORCH_CHECK(t->is_cuda() && t->scalar_type() == at::kInt &&
+                    t->is_contiguous() && t->dim() == 1 && t->size(0) == T,
+                "pos/slot must be contiguous int32 [T] device tensors");
+  }
+  TORCH_CHECK(cos_t.dim() == 2 && cos_t.size(1) == 64 &&
+                  cos_t.size(0) >= 1 && sin_t.sizes() == cos_t.sizes(),
+              "cos/sin must be [S, 64] (head_dim 128)");
+  const long nh = qkv.size(1) / 128;
+  const int Hq = (int)nh - 2 * Hkv;
+  TORCH_CHECK(Hq >= 1 && qkv.size(1) == nh * 128, "qkv width mismatch");
+  TORCH_CHECK(Hq % Hkv == 0, "GQA group mismatch");
+  const int rope_rows = (int)std::min<long>(cos_t.size(0), 1L << 30);
+  auto q = at::empty({T, (long)Hq, 128}, qkv.options());
+  paged_prefill_rope_cache_launch(
+      qkv.data_ptr(), q.data_ptr(), kpool.data_ptr(), vpool.data_ptr(),
+      cos_t.data_ptr(), sin_t.data_ptr(), pos.data_ptr(), slot.data_ptr(), T,
+      Hq, Hkv, pool_rows, rope_rows, cur_stream());
+  return q;
+}
+
 // ---- fused residual add + rmsnorm (inference) ------------------------------
 // s = x + res, y = rmsnorm(s) * w; returns (s, y). res omitted -> plain
 // rmsnorm (s aliases x).
@@ -758,6 +841,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("paged_decode_attn", &paged_decode_attn);
   m.def("paged_decode_rope_cache", &paged_decode_rope_cache);
   m.def("paged_prefill_attn", &paged_prefill_attn);
+  m.def("paged_prefill_attn_ragged", &paged_prefill_attn_ragged);
+  m.def("paged_prefill_rope_cache", &paged_prefill_rope_cache);
   m.def("rmsnorm_res", &rmsnorm_res,
         py::arg("x"), py::arg("res"), py::arg("w"), py::arg("eps"));
 }

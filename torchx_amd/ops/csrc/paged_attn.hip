@@ -340,3 +340,87 @@ extern "C" void paged_decode_rope_cache_launch(
                      (const float*)sin_t, (const int*)pos_dev, B, Hq, Hkv,
                      num_pages, logP, M, rope_rows);
 }
+
+// Fused rope + page append for a packed prefill: qkv [T, (Hq+2*Hkv)*128]
+// is the wqkv output of T tokens of any mix of sequences; token t sits at
+// logical position pos[t] and its K/V row goes to physical pool row
+// slot[t] (= page * P + pos % P, worked out once per forward pass from the
+// block table). Writes the roped q [T, Hq, 128], the roped k and the raw v.
+// One dispatch for the split, the three contiguous copies, the two ropes
+// and the two index_copy_ of the unfused path; the rotation is
+// rope_fwdbwd_kernel's expression, so q and the stored rows are
+// bit-identical to it.
+//
+// 8 lanes per (token, head): lane i8 owns the rotation pairs
+// (8*i8 + j, 64 + 8*i8 + j), j = 0..7 — two 16-byte loads, two 16-byte
+// stores, and 2 x 2 float4 of the tables. pos is clamped to the rope
+// table, slot to [0, num_pages * P), offsets are 64-bit.
+__global__ void __launch_bounds__(256)
+paged_prefill_rope_cache_kernel(const unsigned short* __restrict__ qkv,
+                                unsigned short* __restrict__ qout,  // [T,Hq,128]
+                                unsigned short* __restrict__ kpool,
+                                unsigned short* __restrict__ vpool,
+                                const float* __restrict__ cos_t,  // [S, 64]
+                                const float* __restrict__ sin_t,
+                                const int* __restrict__ pos_dev,   // [T]
+                                const int* __restrict__ slot_dev,  // [T]
+                                long T, int Hq, int Hkv, long pool_rows,
+                                int rope_rows) {
+  typedef float f4 __attribute__((ext_vector_type(4)));
+  const int nh = Hq + 2 * Hkv;
+  const long n = T * nh * 8;
+  for (long i = grid_stride_begin(); i < n; i += grid_stride()) {
+    const int i8 = (int)(i & 7);
+    const long th = i >> 3;
+    const long t = th / nh;
+    const int h = (int)(th - t * nh);
+    const unsigned short* src = qkv + th * HD + i8 * 8;
+    ushort8 u1 = *(const ushort8*)src;
+    ushort8 u2 = *(const ushort8*)(src + 64);
+    unsigned short* dst;
+    if (h < Hq) {
+      dst = qout + (t * Hq + h) * HD;
+    } else {
+      const long slot = min(max((long)slot_dev[t], 0L), pool_rows - 1);
+      dst = (h < Hq + Hkv) ? kpool + (slot * Hkv + (h - Hq)) * HD
+                           : vpool + (slot * Hkv + (h - Hq - Hkv)) * HD;
+    }
+    dst += i8 * 8;
+    if (h < Hq + Hkv) {  // q or k head: rotate
+      const int pos = min(max(pos_dev[t], 0), rope_rows - 1);
+      const float* cp = cos_t + (long)pos * 64 + i8 * 8;
+      const float* sp = sin_t + (long)pos * 64 + i8 * 8;
+      const f4 c0 = *(const f4*)cp, c1 = *(const f4*)(cp + 4);
+      const f4 s0 = *(const f4*)sp, s1 = *(const f4*)(sp + 4);
+      ushort8 o1, o2;
+      #pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const float c = j < 4 ? c0[j & 3] : c1[j & 3];
+        const float s = j < 4 ? s0[j & 3] : s1[j & 3];
+        const float x1 = bf16_to_f32(u1[j]);
+        const float x2 = bf16_to_f32(u2[j]);
+        o1[j] = f32_to_bf16(fmaf(x1, c, -s * x2));
+        o2[j] = f32_to_bf16(fmaf(x2, c, s * x1));
+      }
+      u1 = o1;
+      u2 = o2;
+    }
+    *(ushort8*)dst = u1;
+    *(ushort8*)(dst + 64) = u2;
+  }
+}
+
+extern "C" void paged_prefill_rope_cache_launch(
+    const void* qkv, void* qout, void* kpool, void* vpool, const void* cos_t,
+    const void* sin_t, const void* pos_dev, const void* slot_dev, long T,
+    int Hq, int Hkv, long pool_rows, int rope_rows, hipStream_t stream) {
+  const long n = T * (Hq + 2 * Hkv) * 8;
+  long grid = (n + 255) / 256;
+  if (grid > 65535 * 8) grid = 65535 * 8;
+  hipLaunchKernelGGL(paged_prefill_rope_cache_kernel, dim3((unsigned)grid),
+                     dim3(256), 0, stream, (const unsigned short*)qkv,
+                     (unsigned short*)qout, (unsigned short*)kpool,
+                     (unsigned short*)vpool, (const float*)cos_t,
+                     (const float*)sin_t, (const int*)pos_dev,
+                     (const int*)slot_dev, T, Hq, Hkv, pool_rows, rope_rows);
+}
