@@ -219,6 +219,39 @@ def bench_paged_prefill_ragged(iters, rounds=5):
           res, "unfused")
 
 
+def bench_fwd_map(B, S, Hq, Hkv, iters, rounds=5):
+    """attn_fwd (causal) under each block map, alternating within each
+    round of one process: "legacy" (map_block_fwd), "adjacent" (the G heads
+    of a unit adjacent on one XCD, tiles ascending) and "balanced" (the
+    same, heaviest tiles first)."""
+    hip = ops.hip_ops(required=True)
+    dev = torch.device("cuda", 0)
+    D = 128
+    scale = D ** -0.5
+    torch.manual_seed(0)
+    q = torch.randn(B, S, Hq, D, device=dev, dtype=torch.bfloat16)
+    k = torch.randn(B, S, Hkv, D, device=dev, dtype=torch.bfloat16)
+    v = torch.randn(B, S, Hkv, D, device=dev, dtype=torch.bfloat16)
+    before = ops.get_attn_fwd_map()
+
+    def run(name):
+        def fn():
+            ops.set_attn_fwd_map(name)
+            return hip.attn_fwd(q, k, v, scale, True)
+        return fn
+
+    fns = {name: run(name) for name in ("legacy", "adjacent", "balanced")}
+    ref = fns["legacy"]()
+    same = all(torch.equal(a, b) for name in ("adjacent", "balanced")
+               for a, b in zip(fns[name](), ref))
+    res = _alternate(fns, iters, rounds)
+    ops.set_attn_fwd_map(before)
+    fl = flops_fwd(B, S, Hq, D, True)
+    _show(f"fwd map B{B} S{S} H{Hq}/{Hkv} bit-identical {same} "
+          f"(legacy {fl / res['legacy'][0] / 1e9:.0f} TF/s, balanced "
+          f"{fl / res['balanced'][0] / 1e9:.0f} TF/s)", res, "legacy")
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--B", type=int, default=4)
@@ -227,9 +260,11 @@ def main():
     p.add_argument("--Hkv", type=int, default=8)
     p.add_argument("--iters", type=int, default=20)
     p.add_argument("--mode", type=str, default="both",
-                   choices=["fwd", "bwd", "both", "paged-prefill",
+                   choices=["fwd", "bwd", "both", "fwd-map", "paged-prefill",
                             "paged-prefill-ragged"],
-                   help="paged-prefill: time paged_prefill_attn at ctx=0 "
+                   help="fwd-map: time attn_fwd at --B/--S/--Hq/--Hkv "
+                        "under each block map (ops.set_attn_fwd_map) in "
+                        "one process; paged-prefill: time paged_prefill_attn at ctx=0 "
                         "against attn_fwd (fixed shapes B4 S4096 and "
                         "B1 S512, H32/8, page sizes 16 and 64); "
                         "paged-prefill-ragged: time the ragged kernel "
@@ -253,6 +288,9 @@ def main():
         bench_paged_prefill_ragged(args.iters)
         return
     B, S, Hq, Hkv, D = args.B, args.S, args.Hq, args.Hkv, 128
+    if args.mode == "fwd-map":
+        bench_fwd_map(B, S, Hq, Hkv, args.iters)
+        return
     if args.dkv_impl is not None:
         ops.set_attn_bwd_dkv_impl(args.dkv_impl)
     if args.dq_mode is not None:

@@ -64,7 +64,7 @@ def main():
 
     hip = ops.hip_ops(required=True)
     for name in ["rope_qkv", "attn_fwd_qkv", "attn_bwd_qkv", "rmsnorm_fwd",
-                 "rmsnorm_bwd", "swiglu_gu_fwd", "swiglu_gu_bwd", "ce_fwd",
+                 "add_rmsnorm_fwd", "rmsnorm_bwd", "swiglu_gu_fwd", "swiglu_gu_bwd", "ce_fwd",
                  "ce_bwd", "adamw_step"]:
         setattr(hip, name, timed(name, getattr(hip, name)))
 

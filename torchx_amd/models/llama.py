@@ -15,7 +15,7 @@ BSHD directly).
 from __future__ import annotations
 
 from dataclasses import dataclass
-from typing import Optional
+from typing import Optional, Tuple
 
 import torch
 import torch.nn as nn
@@ -108,21 +108,30 @@ class LlamaBlock(nn.Module):
         self.mlp_norm = nn.Parameter(torch.ones(h, dtype=torch.bfloat16))
 
     def forward(self, x: torch.Tensor, cos: torch.Tensor,
-                sin: torch.Tensor) -> torch.Tensor:
+                sin: torch.Tensor, delta: Optional[torch.Tensor] = None
+                ) -> Tuple[torch.Tensor, torch.Tensor]:
+        """Returns ``(x, delta)``: the block's output is ``x + delta``, and
+        that add is left to the norm that consumes it (the next block's
+        attn_norm or the model's final_norm) — every residual add runs
+        inside ops.add_rmsnorm.  ``delta`` in is the previous block's
+        pending add (None for the first block)."""
         cfg = self.cfg
         B, S, H = x.shape
         # attention: rope + flash straight off the packed qkv GEMM output
         # (no split/cat/contiguous traffic — ops.fused_attention_qkv)
-        xn = ops.rmsnorm(x, self.attn_norm, cfg.rms_eps)
+        if delta is None:
+            xn = ops.rmsnorm(x, self.attn_norm, cfg.rms_eps)
+        else:
+            x, xn = ops.add_rmsnorm(x, delta, self.attn_norm, cfg.rms_eps)
         qkv = _lin(self.wqkv, xn)
         attn = ops.fused_attention_qkv(
             qkv, cos, sin, cfg.num_heads, cfg.num_kv_heads, causal=True
         )
-        x = x + _lin(self.wo, attn.reshape(B, S, cfg.q_dim))
+        x, xn = ops.add_rmsnorm(
+            x, _lin(self.wo, attn.reshape(B, S, cfg.q_dim)), self.mlp_norm,
+            cfg.rms_eps)
         # mlp: swiglu over the packed gate|up buffer
-        xn = ops.rmsnorm(x, self.mlp_norm, cfg.rms_eps)
-        x = x + _lin(self.wdown, ops.swiglu_packed(_lin(self.wgu, xn)))
-        return x
+        return x, _lin(self.wdown, ops.swiglu_packed(_lin(self.wgu, xn)))
 
 
 class LlamaModel(nn.Module):
@@ -160,9 +169,13 @@ class LlamaModel(nn.Module):
     def forward_hidden(self, tokens: torch.Tensor) -> torch.Tensor:
         x = self.embed(tokens)
         cos, sin = self.rope_cos, self.rope_sin
+        delta = None  # the last residual add, fused into the next norm
         for blk in self.blocks:
-            x = blk(x, cos, sin)
-        return ops.rmsnorm(x, self.final_norm, self.cfg.rms_eps)
+            x, delta = blk(x, cos, sin, delta)
+        if delta is None:
+            return ops.rmsnorm(x, self.final_norm, self.cfg.rms_eps)
+        return ops.add_rmsnorm(x, delta, self.final_norm,
+                               self.cfg.rms_eps)[1]
 
     def forward(self, tokens: torch.Tensor,
                 targets: Optional[torch.Tensor] = None) -> torch.Tensor:

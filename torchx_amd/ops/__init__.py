@@ -86,6 +86,46 @@ def rmsnorm(x: torch.Tensor, w: torch.Tensor, eps: float = 1e-5) -> torch.Tensor
     return reference.rmsnorm(x, w, eps)
 
 
+class _AddRMSNorm(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x: torch.Tensor, delta: torch.Tensor, w: torch.Tensor,
+                eps: float):
+        s, y, invrms = hip_ops().add_rmsnorm_fwd(
+            x.contiguous(), delta.contiguous(), w.contiguous(), eps)
+        ctx.save_for_backward(s, w, invrms)
+        # an unused output (s behind the final norm) arrives as None, not
+        # as a zero tensor to be added
+        ctx.set_materialize_grads(False)
+        return s, y
+
+    @staticmethod
+    def backward(ctx, ds: Optional[torch.Tensor],
+                 dy: Optional[torch.Tensor]):
+        if dy is None:
+            return ds, ds, None, None
+        s, w, invrms = ctx.saved_tensors
+        # ds rides along: the dx kernel adds it to its own (bf16-rounded)
+        # dx, which is the accumulate-add autograd would run at the fork
+        dx, dw = hip_ops().rmsnorm_bwd(
+            dy.contiguous(), s, w, invrms,
+            ds.contiguous() if ds is not None else None)
+        return dx, dx, dw.to(w.dtype), None
+
+
+def add_rmsnorm(x: torch.Tensor, delta: torch.Tensor, w: torch.Tensor,
+                eps: float = 1e-5) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Residual add fused into the RMSNorm that consumes it: returns
+    ``(s, y)`` with ``s = x + delta`` (the new residual stream, bf16) and
+    ``y = rmsnorm(s, w)``. One kernel forward and one dx kernel backward
+    instead of add + norm and norm-dx + accumulate-add; outputs and the
+    grads of ``x``, ``delta`` and ``w`` are bit-identical to the unfused
+    pair."""
+    if _on_gpu(x):
+        return _AddRMSNorm.apply(x, delta, w, eps)
+    s = x + delta
+    return s, reference.rmsnorm(s, w, eps)
+
+
 # ---------------------------------------------------------------------------
 # RoPE
 # ---------------------------------------------------------------------------
@@ -320,6 +360,20 @@ def set_attn_bwd_dkv_impl(impl: str) -> None:
 
 def get_attn_bwd_dkv_impl() -> str:
     return hip_ops().get_attn_bwd_dkv_impl()
+
+
+def set_attn_fwd_map(name: str) -> None:
+    """Select the block map of the dense attention forward: "balanced"
+    (default; the G heads of a (batch, kv head, q tile) adjacent on one
+    XCD, heaviest tiles dispatched first), "legacy" (whole (batch, kv head)
+    groups, q tiles ascending) or "adjacent" (the balanced layout with
+    tiles ascending, for A/B).  All produce the same bits.  The initial
+    value comes from TORCHX_AMD_FWD_MAP."""
+    hip_ops().set_attn_fwd_map(name)
+
+
+def get_attn_fwd_map() -> str:
+    return hip_ops().get_attn_fwd_map()
 
 
 def flash_attention(

@@ -260,6 +260,50 @@ __device__ __forceinline__ void map_block_fwd(int B, int Hq, int Hkv,
   }
 }
 
+// Balanced map of the dense forward (attn_fwd_kernel; the dQ kernels keep
+// map_block_fwd).  Under the causal mask q tile qt costs ~qt+1 units, and
+// map_block_fwd walks each head with qt ascending, so an XCD's last
+// dispatched blocks are its heaviest and the kernel ends on their tail.
+//
+// A unit is a (b, kv head, q tile) and owns G = Hq / Hkv blocks, one per q
+// head of the group; with xcd = bid & 7, slot = bid >> 3 the blocks of a
+// unit are adjacent in dispatch order and sit on one XCD.
+//   B*Hkv % 8 == 0: XCD x owns the ns = B*Hkv/8 streams x, x+8, ... — the
+//     streams map_block_fwd gives it, so a K/V stream still lives in one
+//     L2.  Its unit u = slot / G is stream u % ns at tile u / ns counted
+//     from the heaviest end: tiles descend, interleaved over the XCD's
+//     streams.  The grid is exactly B*Hq*nqt.
+//   otherwise: unit = (slot / G) * 8 + xcd over all B*Hkv*nqt units, tile
+//     unit / (B*Hkv) from the heaviest end, stream unit % (B*Hkv); the grid
+//     is rounded up to whole rounds of 8 units (attn_fwd_launch) and a block
+//     of a unit past the end returns false: it must leave before any
+//     barrier.
+// heavy = 0 keeps the unit layout with tiles ascending (A/B of the two
+// steps).  Every (b, hq, qt) is produced exactly once for every shape.
+__device__ __forceinline__ bool map_block_fwd_balanced(int B, int Hq, int Hkv,
+                                                       int nqt, int G,
+                                                       int heavy, int* b,
+                                                       int* hq, int* qt) {
+  const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
+  const int u = slot / G;
+  const int nstream = B * Hkv;
+  int g, t;
+  if ((nstream & 7) == 0) {
+    const int ns = nstream >> 3;
+    g = (u % ns) * 8 + xcd;
+    t = u / ns;
+  } else {
+    const int unit = u * 8 + xcd;
+    if (unit >= nstream * nqt) return false;
+    g = unit % nstream;
+    t = unit / nstream;
+  }
+  *b = g / Hkv;
+  *hq = (g % Hkv) * G + slot % G;
+  *qt = heavy ? nqt - 1 - t : t;
+  return true;
+}
+
 // Build the rot-placed transposed image from a staged swizzled natural
 // image: per thread NCHUNK b128 LDS reads + 8 scalar writes each.  The
 // source tile arrived by glds earlier in the iteration, so the transpose
@@ -314,7 +358,8 @@ attn_fwd_kernel(const unsigned short* __restrict__ q,
                 unsigned short* __restrict__ o,
                 float* __restrict__ lse,  // [B,Hq,S]
                 int B, int S, int Hq, int Hkv, float scale, int causal,
-                long q_rs, long kv_rs) {  // per-seq-row element strides
+                long q_rs, long kv_rs,    // per-seq-row element strides
+                int map) {  // 0 map_block_fwd, 1 balanced, 2 adjacent
   // K and V natural 2-rings (glds); the PV A-operand (V^T) is read off
   // the natural V image with hardware transpose reads (T10) — no V^T
   // build, 64 KiB LDS -> true 2 blocks/CU.
@@ -324,7 +369,12 @@ attn_fwd_kernel(const unsigned short* __restrict__ q,
   const int nqt = (S + BQ - 1) / BQ;
   const int G = Hq / Hkv;
   int b, hq, qt;
-  map_block_fwd(B, Hq, Hkv, nqt, G, &b, &hq, &qt);
+  if (map == 0) {
+    map_block_fwd(B, Hq, Hkv, nqt, G, &b, &hq, &qt);
+  } else if (!map_block_fwd_balanced(B, Hq, Hkv, nqt, G, map == 1, &b, &hq,
+                                     &qt)) {
+    return;  // block-uniform: a padding unit of the rounded-up grid
+  }
   const int hkv = hq / G;
 
   const int wave = threadIdx.x / 64;
@@ -2047,6 +2097,28 @@ attn_bwd_dkv_merged_kernel(const unsigned short* __restrict__ q,
 // ---------------------------------------------------------------------------
 // Launchers
 // ---------------------------------------------------------------------------
+// Block map of attn_fwd_kernel<4>: 0 = map_block_fwd ("legacy"),
+// 1 = balanced (unit-adjacent, heaviest first), 2 = unit-adjacent with
+// tiles ascending.  Initial value from TORCHX_AMD_FWD_MAP, read once; the
+// setter switches it at run time so one process can run all of them.
+#define ATTN_FWD_MAP_DEFAULT 1
+static int g_fwd_map = -1;
+
+extern "C" int attn_fwd_map_get() {
+  if (g_fwd_map < 0) {
+    const char* e = getenv("TORCHX_AMD_FWD_MAP");
+    g_fwd_map = !e ? ATTN_FWD_MAP_DEFAULT
+              : strcmp(e, "legacy") == 0 ? 0
+              : strcmp(e, "balanced") == 0 ? 1
+              : strcmp(e, "adjacent") == 0 ? 2 : ATTN_FWD_MAP_DEFAULT;
+  }
+  return g_fwd_map;
+}
+
+extern "C" void attn_fwd_map_set(int map) {
+  g_fwd_map = (map >= 0 && map <= 2) ? map : ATTN_FWD_MAP_DEFAULT;
+}
+
 extern "C" void attn_fwd_launch(const void* q, const void* k, const void* v,
                                 void* o, void* lse, int B, int S, int Hq,
                                 int Hkv, float scale, int causal,
@@ -2067,14 +2139,21 @@ extern "C" void attn_fwd_launch(const void* q, const void* k, const void* v,
                        0, stream, (const unsigned short*)q,
                        (const unsigned short*)k, (const unsigned short*)v,
                        (unsigned short*)o, (float*)lse, B, S, Hq, Hkv,
-                       scale, causal, q_rs, kv_rs);
+                       scale, causal, q_rs, kv_rs, 0);
   } else {
     const int nqt = (S + 4 * QBLK - 1) / (4 * QBLK);
-    hipLaunchKernelGGL((attn_fwd_kernel<4>), dim3(B * Hq * nqt), dim3(256),
+    const int map = attn_fwd_map_get();
+    // the balanced maps' fallback rounds the grid up to whole rounds of 8
+    // units of G blocks (map_block_fwd_balanced)
+    long grid = (long)B * Hq * nqt;
+    if (map != 0 && ((B * Hkv) & 7) != 0) {
+      grid = ((long)B * Hkv * nqt + 7) / 8 * 8 * (Hq / Hkv);
+    }
+    hipLaunchKernelGGL((attn_fwd_kernel<4>), dim3((unsigned)grid), dim3(256),
                        0, stream, (const unsigned short*)q,
                        (const unsigned short*)k, (const unsigned short*)v,
                        (unsigned short*)o, (float*)lse, B, S, Hq, Hkv,
-                       scale, causal, q_rs, kv_rs);
+                       scale, causal, q_rs, kv_rs, map);
   }
 }
 

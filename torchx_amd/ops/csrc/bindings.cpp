@@ -14,7 +14,8 @@ void swiglu_bwd_launch(const void*, const void*, const void*, void*, void*,
 void rmsnorm_fwd_launch(const void*, const void*, void*, void*, long, int,
                         float, hipStream_t);
 void rmsnorm_bwd_launch(const void*, const void*, const void*, const void*,
-                        void*, void*, void*, long, int, hipStream_t);
+                        const void*, void*, void*, void*, long, int,
+                        hipStream_t);
 long rmsnorm_bwd_dw_chunks(long);
 void adamw_launch(void*, void*, const void*, void*, void*, long, float, float,
                   float, float, float, float, float, hipStream_t);
@@ -31,6 +32,8 @@ void attn_bwd_launch(const void*, const void*, const void*, const void*,
 long attn_bwd_ds_bytes(int, int, int, int);
 int attn_bwd_dkv_impl_get();
 void attn_bwd_dkv_impl_set(int);
+int attn_fwd_map_get();
+void attn_fwd_map_set(int);
 void rope_qkv_launch(const void*, void*, const void*, const void*, long, int,
                      long, int, float, hipStream_t);
 void swiglu_gu_fwd_launch(const void*, void*, long, long, hipStream_t);
@@ -54,7 +57,7 @@ void decode_rope_cache_launch(const void*, void*, void*, void*, const void*,
                               const void*, const void*, int, int, int, int,
                               int, int, hipStream_t);
 void rmsnorm_res_launch(const void*, const void*, const void*, void*, void*,
-                        long, int, float, hipStream_t);
+                        void*, long, int, float, hipStream_t);
 void gemv_swiglu_launch(const void*, const void*, void*, int, int, int,
                         hipStream_t);
 void paged_decode_attn_launch(const void*, const void*, const void*, void*,
@@ -113,19 +116,34 @@ std::vector<at::Tensor> rmsnorm_fwd(at::Tensor x, at::Tensor w, double eps) {
   return {y, invrms};
 }
 
+// dres (optional): the gradient that reaches the norm's input along the
+// residual stream; dx is then bf16(dx) + dres, the bits of the separate
+// accumulate-add (add_rmsnorm backward).
 std::vector<at::Tensor> rmsnorm_bwd(at::Tensor dy, at::Tensor x, at::Tensor w,
-                                    at::Tensor invrms) {
+                                    at::Tensor invrms,
+                                    c10::optional<at::Tensor> dres) {
   check_bf16(dy, "dy");
   check_bf16(x, "x");
+  check_bf16(w, "w");
+  check_f32(invrms, "invrms");
   const long H = x.size(-1);
   TORCH_CHECK(H % 2048 == 0 && H <= 8192, "rmsnorm: H must be k*2048, <=8192");
   const long rows = x.numel() / H;
+  TORCH_CHECK(dy.sizes() == x.sizes(), "dy shape mismatch");
+  TORCH_CHECK(w.numel() == H && invrms.numel() == rows,
+              "w / invrms size mismatch");
+  const void* rp = nullptr;
+  if (dres.has_value()) {
+    check_bf16(*dres, "dres");
+    TORCH_CHECK(dres->sizes() == x.sizes(), "dres shape mismatch");
+    rp = dres->data_ptr();
+  }
   auto dx = at::empty_like(x);
   auto dw = at::empty({H}, x.options().dtype(at::kFloat));
   // per-row-chunk partial sums of dw, reduced in a fixed order
   auto dw_part = at::empty({rmsnorm_bwd_dw_chunks(rows), H}, dw.options());
   rmsnorm_bwd_launch(dy.data_ptr(), x.data_ptr(), w.data_ptr(),
-                     invrms.data_ptr(), dx.data_ptr(), dw.data_ptr(),
+                     invrms.data_ptr(), rp, dx.data_ptr(), dw.data_ptr(),
                      dw_part.data_ptr(), rows, (int)H, cur_stream());
   return {dx, dw};
 }
@@ -266,6 +284,24 @@ void set_attn_bwd_dkv_impl(const std::string& impl) {
 
 std::string get_attn_bwd_dkv_impl() {
   return attn_bwd_dkv_impl_get() == 1 ? "merged" : "split";
+}
+
+// Block map of the dense forward kernel.  "legacy": map_block_fwd (whole
+// (b, kv head) groups per XCD, q tiles ascending); "balanced": the G heads
+// of a (b, kv head, q tile) unit adjacent on one XCD, units heaviest first;
+// "adjacent": the same unit layout with q tiles ascending (A/B only).  All
+// give the same bits.  Initial value from TORCHX_AMD_FWD_MAP (read once by
+// the launcher).
+void set_attn_fwd_map(const std::string& name) {
+  TORCH_CHECK(name == "legacy" || name == "balanced" || name == "adjacent",
+              "attn fwd map must be 'balanced', 'legacy' or 'adjacent', "
+              "got '", name, "'");
+  attn_fwd_map_set(name == "legacy" ? 0 : name == "balanced" ? 1 : 2);
+}
+
+std::string get_attn_fwd_map() {
+  const int m = attn_fwd_map_get();
+  return m == 0 ? "legacy" : m == 1 ? "balanced" : "adjacent";
 }
 
 // The scratch is transient HBM on top of the saved activations and grows
@@ -778,9 +814,31 @@ std::vector<at::Tensor> rmsnorm_res(at::Tensor x,
     rp = res->data_ptr();
     sp = s.data_ptr();
   }
-  rmsnorm_res_launch(x.data_ptr(), rp, w.data_ptr(), sp, y.data_ptr(), R,
-                     (int)H, (float)eps, cur_stream());
+  rmsnorm_res_launch(x.data_ptr(), rp, w.data_ptr(), sp, y.data_ptr(),
+                     nullptr, R, (int)H, (float)eps, cur_stream());
   return {s, y};
+}
+
+// ---- fused residual add + rmsnorm (training) -------------------------------
+// s = bf16(x + delta), y = rmsnorm(s) * w; returns (s, y, invrms) with
+// invrms [rows] f32 saved for rmsnorm_bwd.
+std::vector<at::Tensor> add_rmsnorm_fwd(at::Tensor x, at::Tensor delta,
+                                        at::Tensor w, double eps) {
+  check_bf16(x, "x");
+  check_bf16(delta, "delta");
+  check_bf16(w, "w");
+  const long H = x.size(-1);
+  TORCH_CHECK(H % 2048 == 0 && H <= 8192, "rmsnorm: H must be k*2048, <=8192");
+  TORCH_CHECK(delta.sizes() == x.sizes(), "delta shape mismatch");
+  TORCH_CHECK(w.numel() == H, "w size mismatch");
+  const long R = x.numel() / H;
+  auto s = at::empty_like(x);
+  auto y = at::empty_like(x);
+  auto invrms = at::empty({R}, x.options().dtype(at::kFloat));
+  rmsnorm_res_launch(x.data_ptr(), delta.data_ptr(), w.data_ptr(),
+                     s.data_ptr(), y.data_ptr(), invrms.data_ptr(), R, (int)H,
+                     (float)eps, cur_stream());
+  return {s, y, invrms};
 }
 
 // ---- probe ----------------------------------------------------------------
@@ -808,7 +866,9 @@ at::Tensor mfma_probe(at::Tensor a, at::Tensor b) {
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("rmsnorm_fwd", &rmsnorm_fwd);
-  m.def("rmsnorm_bwd", &rmsnorm_bwd);
+  m.def("rmsnorm_bwd", &rmsnorm_bwd, py::arg("dy"), py::arg("x"),
+        py::arg("w"), py::arg("invrms"), py::arg("dres") = c10::nullopt);
+  m.def("add_rmsnorm_fwd", &add_rmsnorm_fwd);
   m.def("rope", &rope);
   m.def("swiglu_fwd", &swiglu_fwd);
   m.def("swiglu_bwd", &swiglu_bwd);
@@ -821,6 +881,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("get_attn_bwd_dq_mode", &get_attn_bwd_dq_mode);
   m.def("set_attn_bwd_dkv_impl", &set_attn_bwd_dkv_impl);
   m.def("get_attn_bwd_dkv_impl", &get_attn_bwd_dkv_impl);
+  m.def("set_attn_fwd_map", &set_attn_fwd_map);
+  m.def("get_attn_fwd_map", &get_attn_fwd_map);
   m.def("attn_fwd_qkv", &attn_fwd_qkv);
   m.def("attn_bwd_qkv", &attn_bwd_qkv);
   m.def("rope_qkv", &rope_qkv);

@@ -70,6 +70,7 @@ rmsnorm_bwd_dx_kernel(
     const unsigned short* __restrict__ x,
     const unsigned short* __restrict__ w,
     const float* __restrict__ invrms,
+    const unsigned short* __restrict__ dres,  // optional [R, H], see below
     unsigned short* __restrict__ dx,
     int H) {
   __shared__ float red[4];
@@ -107,6 +108,16 @@ rmsnorm_bwd_dx_kernel(
     #pragma unroll
     for (int j = 0; j < 8; ++j) {
       ov[j] = f32_to_bf16(fmaf(dyw[it][j], r, -xs[it][j] * kk));
+    }
+    if (dres) {
+      // the residual fork's accumulate-add, fused: the norm's dx is rounded
+      // to bf16 first (what the plain kernel stores), then added the way
+      // the bf16 tensor add does — same bits as dx kernel + add
+      ushort8 rv = *(const ushort8*)(dres + row * (long)H + i);
+      #pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        ov[j] = f32_to_bf16(bf16_to_f32(ov[j]) + bf16_to_f32(rv[j]));
+      }
     }
     *(ushort8*)(dxr + i) = ov;
   }
@@ -191,15 +202,19 @@ extern "C" void rmsnorm_fwd_launch(const void* x, const void* w, void* y,
 }
 
 extern "C" void rmsnorm_bwd_launch(const void* dy, const void* x,
-                                   const void* w, const void* invrms, void* dx,
-                                   void* dw, void* dw_part, long rows, int H,
+                                   const void* w, const void* invrms,
+                                   const void* dres, void* dx, void* dw,
+                                   void* dw_part, long rows, int H,
                                    hipStream_t stream) {
   // dw_part: f32 scratch of rmsnorm_bwd_dw_chunks(rows) * H elements
+  // dres: null, or the gradient arriving on the residual stream next to the
+  // norm; dx then holds bf16(dx) + dres (training add_rmsnorm backward)
 #define LAUNCH_B(I)                                                            \
   hipLaunchKernelGGL((rmsnorm_bwd_dx_kernel<I>), dim3((int)rows), dim3(256),   \
                      0, stream, (const unsigned short*)dy,                     \
                      (const unsigned short*)x, (const unsigned short*)w,       \
-                     (const float*)invrms, (unsigned short*)dx, H)
+                     (const float*)invrms, (const unsigned short*)dres,      \
+                     (unsigned short*)dx, H)
   DISPATCH_ITERS(H, LAUNCH_B);
 #undef LAUNCH_B
   const int row_chunks = (int)rmsnorm_bwd_dw_chunks(rows);
@@ -213,11 +228,13 @@ extern "C" void rmsnorm_bwd_launch(const void* dy, const void* x,
                      stream, (const float*)dw_part, (float*)dw, row_chunks, H);
 }
 
-// Fused residual-add + RMSNorm (decode/inference): s = x + res (the new
-// residual stream), y = rmsnorm(s) * w. Same one-block-per-row shape as
-// the forward kernel; res == nullptr degrades to plain rmsnorm with no s
-// write. No invrms save — inference only, replaces an elementwise add +
-// rmsnorm pair (2 dispatches -> 1) per use in the decode step.
+// Fused residual-add + RMSNorm: s = x + res (the new residual stream),
+// y = rmsnorm(s) * w. Same one-block-per-row shape, expressions and
+// reduction as the forward kernel, so y and invrms are the bits of a bf16
+// tensor add followed by rmsnorm_fwd_kernel; res == nullptr degrades to
+// plain rmsnorm with no s write. Replaces an elementwise add + rmsnorm pair
+// (2 dispatches -> 1, 5 activation passes -> 4). invrms == nullptr is the
+// decode/inference use (nothing saved); training (add_rmsnorm) passes it.
 template <int ITERS>  // ITERS = H / (256 * 8)
 __global__ void __launch_bounds__(256)
 rmsnorm_res_fwd_kernel(const unsigned short* __restrict__ x,
@@ -225,6 +242,7 @@ rmsnorm_res_fwd_kernel(const unsigned short* __restrict__ x,
                        const unsigned short* __restrict__ w,
                        unsigned short* __restrict__ s_out,
                        unsigned short* __restrict__ y,
+                       float* __restrict__ invrms,  // [R] or null
                        int H, float eps) {
   __shared__ float red[4];
   const long row = blockIdx.x;
@@ -256,6 +274,7 @@ rmsnorm_res_fwd_kernel(const unsigned short* __restrict__ x,
   float total = block_reduce<4>(acc, red,
       [] __device__ (float a, float b) { return a + b; });
   float r = rsqrtf(total / (float)H + eps);
+  if (invrms && threadIdx.x == 0) invrms[row] = r;
 
   #pragma unroll
   for (int it = 0; it < ITERS; ++it) {
@@ -272,7 +291,7 @@ rmsnorm_res_fwd_kernel(const unsigned short* __restrict__ x,
 
 extern "C" void rmsnorm_res_launch(const void* x, const void* res,
                                    const void* w, void* s_out, void* y,
-                                   long R, int H, float eps,
+                                   void* invrms, long R, int H, float eps,
                                    hipStream_t stream) {
   #define RMSRES_CASE(N)                                                   \
     case N:                                                                \
@@ -280,7 +299,7 @@ extern "C" void rmsnorm_res_launch(const void* x, const void* res,
                          0, stream, (const unsigned short*)x,              \
                          (const unsigned short*)res,                       \
                          (const unsigned short*)w, (unsigned short*)s_out, \
-                         (unsigned short*)y, H, eps);                      \
+                         (unsigned short*)y, (float*)invrms, H, eps);      \
       break;
   switch (H / 2048) {
     RMSRES_CASE(1)
