@@ -14,6 +14,17 @@ Layouts measured per shape (M tokens, N out, K in), weight W [N,K]:
   dgrad-NT  dy[M,N] @ Wt^T
   wgrad-TN  dy^T[N,M] @ x         (dW [N,K])
   wgrad-TN' x^T[K,M] @ dy         (dWt [K,N])
+
+Correction (r9a): the case names above are torch-side, and the rates quoted
+in the first paragraph have two of them swapped. In BLAS terms `x @ W^T`
+(fwd-NT here, and dgrad-NT) is a TN GEMM — both operands contiguous along
+the reduction dimension — and runs the Custom `Cijk_Alik_Bljk ... SK3
+MT256x256x64` kernel, the fast one (~1.5 PF/s). `dy^T @ x` (wgrad-TN here)
+is BLAS NT — both operands strided along the reduction dimension M — and
+runs `Cijk_Ailk_Bjlk MT256x256x32`, the slow one (~1.05 PF/s in the step).
+The call counts of the committed profiles prove the mapping
+(profiles/README.md, r9a). `--wgrad` compares the wgrad's operand forms,
+including dyT @ xT^T, which is BLAS TN like the forward.
 """
 
 import argparse
@@ -60,8 +71,73 @@ def bench_mm_cold(fn, iters=8, warmup=2):
     return total / iters
 
 
+def wgrad_forms(args, shapes, dev):
+    """The wgrad dW[N,K] = dy^T x in its operand forms, LLC flushed between
+    calls, timed by events:
+      wgrad-TN     dy.t() @ x        (BLAS NT: both operands strided in M)
+      wgrad-viaT   dyT @ x           incl. transpose_bf16(dy)   (BLAS NN)
+      wgrad-TT     dyT @ xT.t()      operands pre-transposed    (BLAS TN)
+      wgrad-TT+tr  the same incl. transpose_bf16 of dy and of x
+    The forms alternate within a repeat; per form the mean of the repeats'
+    means and their spread (max - min) are reported in ms."""
+    sys.path.insert(0, __import__("os").path.dirname(__import__(
+        "os").path.dirname(__import__("os").path.abspath(__file__))))
+    from torchx_amd import ops as _txops
+    hip = _txops.hip_ops(required=True)
+    M = args.m
+    step_gain = 0.0
+    for name, N, K in shapes:
+        if args.shape and name != args.shape:
+            continue
+        x = torch.randn(M, K, device=dev, dtype=torch.bfloat16)
+        dy = torch.randn(M, N, device=dev, dtype=torch.bfloat16)
+        xT = hip.transpose_bf16(x)
+        dyT = hip.transpose_bf16(dy)
+        cases = {
+            "wgrad-TN": lambda: dy.t() @ x,
+            "wgrad-viaT": lambda: hip.transpose_bf16(dy) @ x,
+            "wgrad-TT": lambda: dyT @ xT.t(),
+            "wgrad-TT+tr": lambda: (hip.transpose_bf16(dy)
+                                    @ hip.transpose_bf16(x).t()),
+        }
+        ms = {c: [] for c in cases}
+        for _ in range(args.repeats):
+            for c, fn in cases.items():
+                ms[c].append(bench_mm_cold(fn, iters=args.iters,
+                                           warmup=args.warmup) * 1e3)
+        flops = 2.0 * M * N * K
+        row = {"shape": name, "M": M, "N": N, "K": K}
+        for c, v in ms.items():
+            mean = sum(v) / len(v)
+            row[c] = {"ms": round(mean, 4),
+                      "spread": round(max(v) - min(v), 4),
+                      "TFs": round(flops / mean / 1e9, 1)}
+        # today's form: via_t for N <= 8192, plain TN otherwise
+        cur = "wgrad-viaT" if N <= 8192 else "wgrad-TN"
+        gain = row[cur]["ms"] - row["wgrad-TT+tr"]["ms"]
+        noise = max(row[cur]["spread"], row["wgrad-TT+tr"]["spread"])
+        per_step = 1 if name == "lm_head" else 32
+        row["current"] = cur
+        row["gain_ms"] = round(gain, 4)
+        row["go"] = bool(gain > noise)
+        if row["go"]:
+            step_gain += gain * per_step
+        print(json.dumps(row), flush=True)
+        del x, dy, xT, dyT
+        torch.cuda.empty_cache()
+    print(json.dumps({"step_gain_ms_of_go_shapes": round(step_gain, 2)}))
+    return 0
+
+
 def main():
     p = argparse.ArgumentParser()
+    p.add_argument("--wgrad", action="store_true",
+                   help="compare the wgrad operand forms (TN, viaT, TT) per "
+                        "shape, LLC flushed, with repeats")
+    p.add_argument("--repeats", type=int, default=3)
+    p.add_argument("--warmup", type=int, default=2)
+    p.add_argument("--shape", default="",
+                   help="with --wgrad: only this shape")
     p.add_argument("--m", type=int, default=16384)
     p.add_argument("--iters", type=int, default=20)
     p.add_argument("--cold", action="store_true",
@@ -181,6 +257,8 @@ def main():
     ]
 
     dev = torch.device("cuda:0")
+    if args.wgrad:
+        return wgrad_forms(args, shapes, dev)
     flat = None
     if args.flat:
         # weights as views into one big flat allocation (the FlatParams

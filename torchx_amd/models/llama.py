@@ -93,6 +93,15 @@ def _new_linear(in_features: int, out_features: int,
                      dtype=torch.bfloat16)
 
 
+def _lin_swiglu(mod: nn.Module, x: torch.Tensor) -> torch.Tensor:
+    """swiglu_packed(_lin(mod, x)) for the packed gate|up projection; on
+    the fast_linear route it is one autograd node (ops.linear_swiglu),
+    whose SwiGLU backward also writes the transposed operand of the wgrad."""
+    if type(mod) is nn.Linear and mod.bias is None and x.is_cuda:
+        return ops.linear_swiglu(x, mod.weight)
+    return ops.swiglu_packed(mod(x))
+
+
 class LlamaBlock(nn.Module):
     def __init__(self, cfg: LlamaConfig,
                  device: Optional[torch.device] = None):
@@ -131,7 +140,7 @@ class LlamaBlock(nn.Module):
             x, _lin(self.wo, attn.reshape(B, S, cfg.q_dim)), self.mlp_norm,
             cfg.rms_eps)
         # mlp: swiglu over the packed gate|up buffer
-        return x, _lin(self.wdown, ops.swiglu_packed(_lin(self.wgu, xn)))
+        return x, _lin(self.wdown, _lin_swiglu(self.wgu, xn))
 
 
 class LlamaModel(nn.Module):

@@ -264,14 +264,23 @@ class _FusedLinearCE(torch.autograd.Function):
             loss_c, lse_c = hip.ce_fwd(logits_c, t_c)
             loss_sum += loss_c.sum()
             dlog_c = hip.ce_bwd(logits_c, t_c, lse_c, gscale[:e - s])
+            # the logits are dead from here: released before dW is allocated
+            del logits_c
             if wt is not None:
                 torch.matmul(dlog_c, wt.t(), out=dx[s:e])
             else:
                 torch.matmul(dlog_c, w, out=dx[s:e])
+            # the wgrad stays dlog^T @ x: from transposed operands (see
+            # _wgrad) it is 13% faster at the lm_head shape, but there the
+            # stream-K TN kernel splits tiles and sums them in another
+            # order — ~10^4 of 5*10^8 elements round to the other bf16,
+            # and 15 AdamW steps turn that into another loss curve. The
+            # wgu shape has no such tiles: same bits either way.
             if single:
                 dw_acc = dlog_c.t() @ x_c
             else:
                 dw_acc += dlog_c.t() @ x_c
+            del dlog_c
         ctx.save_for_backward(dx, dw_acc)
         return loss_sum * inv_t
 
@@ -436,33 +445,51 @@ class _FastLinear(torch.autograd.Function):
         dy2 = dy.reshape(-1, dy.shape[-1]).contiguous()
         x2 = x.reshape(-1, x.shape[-1])
         dx = (dy2 @ wt.t()).view_as(x)
-        # wgrad: for narrow outputs (qkv/wo/down shapes) transposing dy
-        # once and running the wgrad as a plain NN GEMM beats the TN form
-        # by ~15% incl. the transpose (tools/gemm_probe.py wgrad-viaT);
-        # fat outputs (gu, lm_head) are neutral and skip the transpose
-        M, N = dy2.shape
-        via_t = N <= 8192 and M % 64 == 0 and N % 64 == 0
-        # direct accumulation: when the param already has a (flat-buffer)
-        # grad slot, the wgrad GEMM accumulates straight into it with
-        # beta=1 — no dw buffer write/read and no AccumulateGrad RMW pass.
-        # Safe because each weight is consumed once per step; the DDP
-        # bucket hook is notified manually (grad_ready).
-        wg = w.grad if w.is_leaf else None
-        if wg is not None and wg.is_contiguous():
-            a = hip.transpose_bf16(dy2) if via_t else dy2.t()
-            if getattr(w, "_wgrad_fresh", False):
-                # first touch since zero_grad: overwrite (beta=0) — skips
-                # both the zeroed-C read in the GEMM and staleness
-                torch.matmul(a, x2, out=wg)
-                w._wgrad_fresh = False
-            else:
-                wg.addmm_(a, x2)
-            from torchx_amd.parallel.ddp import grad_ready
+        return dx, _wgrad(hip, w, dy2, x2)
 
-            grad_ready(w)
-            return dx, None
-        dw = (hip.transpose_bf16(dy2) @ x2) if via_t else (dy2.t() @ x2)
-        return dx, dw
+
+def _wgrad(hip, w: torch.Tensor, dy2: torch.Tensor, x2: torch.Tensor,
+           dyt: Optional[torch.Tensor] = None) -> Optional[torch.Tensor]:
+    """dW [N, K] = dy2^T [N, M] @ x2 [M, K] of a fast_linear weight, in the
+    operand form that tools/gemm_probe.py --wgrad measures fastest for the
+    shape (transposes included):
+      - fat outputs (the gu shape): both operands transposed,
+        dyT @ xT^T — both contiguous along the reduction dimension M, which
+        is the form of the forward GEMM (~1.35 vs ~1.2 PF/s); at the gu
+        shape the result has the bits of dy^T @ x;
+      - narrow outputs (qkv/wo/down shapes): dy transposed once, dyT @ x;
+        transposing x as well gains less than its own transpose costs;
+      - M or N not a multiple of 64: plain dy^T @ x.
+    ``dyt`` is dy2 already transposed, if the producer of dy2 had it.
+    Returns dW, or None after accumulating into the weight's grad slot."""
+    M, N = dy2.shape
+    K = x2.shape[1]
+    aligned = M % 64 == 0 and N % 64 == 0
+    both_t = aligned and N > 8192 and K % 64 == 0
+    if both_t or (aligned and N <= 8192):
+        a = dyt if dyt is not None else hip.transpose_bf16(dy2)
+    else:
+        a = dy2.t()
+    b = hip.transpose_bf16(x2.contiguous()).t() if both_t else x2
+    # direct accumulation: when the param already has a (flat-buffer)
+    # grad slot, the wgrad GEMM accumulates straight into it with
+    # beta=1 — no dw buffer write/read and no AccumulateGrad RMW pass.
+    # Safe because each weight is consumed once per step; the DDP
+    # bucket hook is notified manually (grad_ready).
+    wg = w.grad if w.is_leaf else None
+    if wg is not None and wg.is_contiguous():
+        if getattr(w, "_wgrad_fresh", False):
+            # first touch since zero_grad: overwrite (beta=0) — skips
+            # both the zeroed-C read in the GEMM and staleness
+            torch.matmul(a, b, out=wg)
+            w._wgrad_fresh = False
+        else:
+            wg.addmm_(a, b)
+        from torchx_amd.parallel.ddp import grad_ready
+
+        grad_ready(w)
+        return None
+    return a @ b
 
 
 def fast_linear(x: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
@@ -544,6 +571,47 @@ def swiglu_packed(gu: torch.Tensor) -> torch.Tensor:
         return _SwiGLUPacked.apply(gu)
     g, u = gu.chunk(2, dim=-1)
     return reference.swiglu(g, u)
+
+
+class _LinearSwiGLU(torch.autograd.Function):
+    """fast_linear + swiglu_packed as one autograd node, so that the SwiGLU
+    backward can hand the wgrad its input already transposed: dgu and
+    dgu^T come out of one kernel (swiglu_gu_bwd_t) instead of dgu being
+    read back by a stand-alone transpose.  Forward and saved tensors are
+    those of the two separate nodes."""
+
+    @staticmethod
+    def forward(ctx, x: torch.Tensor, w: torch.Tensor):
+        hip = hip_ops()
+        gu = x @ w.t()
+        ctx.save_for_backward(x, w, gu)
+        return hip.swiglu_gu_fwd(gu)
+
+    @staticmethod
+    def backward(ctx, dout: torch.Tensor):
+        x, w, gu = ctx.saved_tensors
+        hip = hip_ops()
+        dout = dout.contiguous()
+        gu2 = gu.view(-1, gu.shape[-1])
+        if gu2.shape[0] % 64 == 0 and gu2.shape[1] % 128 == 0:
+            dgu2, dgut = hip.swiglu_gu_bwd_t(dout.view(-1, dout.shape[-1]),
+                                             gu2)
+        else:
+            dgu2, dgut = hip.swiglu_gu_bwd(dout, gu2), None
+        wt = hip.transpose_bf16(w)                      # [K, N]
+        dx = (dgu2 @ wt.t()).view_as(x)
+        return dx, _wgrad(hip, w, dgu2, x.reshape(-1, x.shape[-1]), dgut)
+
+
+def linear_swiglu(x: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
+    """``swiglu_packed(fast_linear(x, w))`` for the packed gate|up weight
+    ``w`` [2I, K]: the same values forward and backward, with the wgrad's
+    transposed operand written by the SwiGLU backward kernel itself. Off
+    the fast path (CPU, dims not 64-aligned) it is the two separate ops."""
+    if (x.is_cuda and w.dtype == torch.bfloat16 and x.dtype == w.dtype
+            and w.shape[0] % 64 == 0 and w.shape[1] % 64 == 0):
+        return _LinearSwiGLU.apply(x, w)
+    return swiglu_packed(fast_linear(x, w))
 
 
 # ---------------------------------------------------------------------------

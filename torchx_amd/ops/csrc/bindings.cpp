@@ -39,6 +39,8 @@ void rope_qkv_launch(const void*, void*, const void*, const void*, long, int,
 void swiglu_gu_fwd_launch(const void*, void*, long, long, hipStream_t);
 void swiglu_gu_bwd_launch(const void*, const void*, void*, long, long,
                           hipStream_t);
+void swiglu_gu_bwd_t_launch(const void*, const void*, void*, void*, long,
+                            long, hipStream_t);
 void mfma_probe_launch(const void*, const void*, void*, hipStream_t);
 void mfma_probe_tr_launch(const void*, const void*, void*, void*,
                           hipStream_t);
@@ -425,6 +427,25 @@ at::Tensor swiglu_gu_bwd(at::Tensor dout, at::Tensor gu) {
   swiglu_gu_bwd_launch(dout.data_ptr(), gu.data_ptr(), dgu.data_ptr(), rows,
                        I, cur_stream());
   return dgu;
+}
+
+// dgu as swiglu_gu_bwd plus dguT [2I, rows] = dgu^T from the same pass.
+std::vector<at::Tensor> swiglu_gu_bwd_t(at::Tensor dout, at::Tensor gu) {
+  check_bf16(dout, "dout");
+  check_bf16(gu, "gu");
+  const long twoI = gu.size(-1);
+  const long I = twoI / 2;
+  const long rows = gu.numel() / twoI;
+  TORCH_CHECK(twoI % 2 == 0 && I % 64 == 0 && rows % 64 == 0 && rows > 0 &&
+                  (rows / 64) * (I / 64) < (1L << 31),
+              "swiglu_gu_bwd_t: rows and I must be multiples of 64");
+  TORCH_CHECK(dout.numel() == rows * I && dout.size(-1) == I,
+              "swiglu_gu_bwd_t: dout must be [rows, I]");
+  auto dgu = at::empty_like(gu);
+  auto dguT = at::empty({twoI, rows}, gu.options());
+  swiglu_gu_bwd_t_launch(dout.data_ptr(), gu.data_ptr(), dgu.data_ptr(),
+                         dguT.data_ptr(), rows, I, cur_stream());
+  return {dgu, dguT};
 }
 
 // ---- fp8 fused cast+transpose ---------------------------------------------
@@ -888,6 +909,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("rope_qkv", &rope_qkv);
   m.def("swiglu_gu_fwd", &swiglu_gu_fwd);
   m.def("swiglu_gu_bwd", &swiglu_gu_bwd);
+  m.def("swiglu_gu_bwd_t", &swiglu_gu_bwd_t);
   m.def("fp8_cast_transpose", &fp8_cast_transpose);
   m.def("mfma_probe", &mfma_probe);
   m.def("mfma_probe_tr", &mfma_probe_tr);
