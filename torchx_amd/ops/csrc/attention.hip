@@ -203,6 +203,28 @@ __device__ __forceinline__ void stage_k_glds(
   }
 }
 
+// stage_k_glds with (wave, lane) as parameters, so that a caller can hand in
+// an opaque copy of the lane id and keep the per-piece lane constants out of
+// its loop-carried registers.
+template <int NW = 4, int TFKV = FKV>
+__device__ __forceinline__ void stage_k_glds_at(
+    const unsigned short* __restrict__ kb, long kv0, long stride_elems,
+    int S, char* kimg, int wave, int lane) {
+  #pragma unroll
+  for (int j = 0; j < (TFKV / 4) / NW; ++j) {
+    const int i = wave * ((TFKV / 4) / NW) + j;
+    const int row = i * 4 + (lane >> 4);
+    const int colbyte = ((lane & 15) * 16) ^ ((row & 15) << 4);
+    long srow = kv0 + row;
+    if (srow >= S) srow = S - 1;
+    const char* src = (const char*)(kb + srow * stride_elems) + colbyte;
+    __builtin_amdgcn_global_load_lds(
+        (const __attribute__((address_space(1))) unsigned int*)src,
+        (__attribute__((address_space(3))) unsigned int*)(kimg + i * 1024),
+        16, 0, 0);
+  }
+}
+
 // V tile -> registers (4 x b128 per thread); written transposed+swizzled
 // into the LDS V^T image after the barrier.
 __device__ __forceinline__ void load_v_regs(
@@ -1653,10 +1675,11 @@ __device__ __forceinline__ void packed_to_frags_swap(const unsigned int* a,
 // is the split kernel's, so dk, dv and the exported dS are bit-identical.
 //
 // At one wave per SIMD nothing hides a latency for free, so the tile body
-// is a hand-staged software pipeline over pairs of 32-q sub-tiles: LDS
-// reads are issued in groups ahead of their MFMAs, and the S/dP chain of
-// the second sub-tile runs chunk by chunk under the mask/exp2 VALU of the
-// first (see the stage list in the loop).  The block mapping, the staged
+// is a hand-staged software pipeline over single 32-q sub-tiles: LDS reads
+// are issued in groups ahead of their MFMAs, and the S/dP chain of the
+// next sub-tile and the dV/dK accumulation of the previous one run chunk
+// by chunk under the mask/exp2 VALU of the current one (see the stage
+// list in the loop).  The block mapping, the staged
 // images, the lse/delta double buffer, the dS image layout and the
 // epilogue are the split kernel's.  The next tile's lse/delta value is
 // loaded into one register at the loop head, next to the glds issue, and
@@ -1789,9 +1812,15 @@ attn_bwd_dkv_merged_kernel(const unsigned short* __restrict__ q,
   store_lse(0, load_lse(0, t0));
   __syncthreads();
 
-  const float* lse_cur = lse_buf[0];
-  const float* del_cur = del_buf[0];
-  int lse_nxt = 1;
+  int lse_nxt = 1;   // lse/delta buffer of the next tile; cur is the other
+  // The accumulators are untouched from the tile head to step 1.  Naming
+  // them there, in their own register file, keeps the allocator from
+  // parking them elsewhere for that stretch and moving all 128 back.
+  auto pin_acc = [&]() __attribute__((always_inline)) {
+    asm volatile("" : "+a"(accv[0]), "+a"(accv[1]), "+a"(accv[2]),
+                      "+a"(accv[3]), "+a"(acck[0]), "+a"(acck[1]),
+                      "+a"(acck[2]), "+a"(acck[3]));
+  };
   for (int idx = 0; idx < total; ++idx) {
     const int gh = idx / nt_eff;
     const int t = t0 + idx % nt_eff;
@@ -1801,15 +1830,21 @@ attn_bwd_dkv_merged_kernel(const unsigned short* __restrict__ q,
     const int ngh = (idx + 1) / nt_eff;
     const int ntile = t0 + (idx + 1) % nt_eff;
     float lse_reg = 0.f;
+    // opaque copy of the lane id: what the tile derives from it (glds
+    // source offsets, LDS read addresses) is recomputed per tile — hoisted
+    // out of the tile loop those lane constants would be spilled around it
+    int lane_t = lane;
+    asm volatile("" : "+v"(lane_t));
+    pin_acc();
     if (has_next) {
       // async glds issue BEFORE compute: their latency hides under the
       // S/dP chain and the softmax of the first sub-tile.  The next
       // tile's lse/delta value rides along in ONE register, so the
       // barrier at the tile end does not wait on a fresh global load.
-      stage_k_glds<4, TFKV>(head_q(ngh), (long)ntile * TFKV, q_seq_stride, S,
-                            qn_n);
-      stage_k_glds<4, TFKV>(head_do(ngh), (long)ntile * TFKV, dout_rs, S,
-                            don_n);
+      stage_k_glds_at<4, TFKV>(head_q(ngh), (long)ntile * TFKV, q_seq_stride,
+                               S, qn_n, wave, lane_t);
+      stage_k_glds_at<4, TFKV>(head_do(ngh), (long)ntile * TFKV, dout_rs, S,
+                               don_n, wave, lane_t);
       lse_reg = load_lse(ngh, ntile);
     }
 
@@ -1824,36 +1859,96 @@ attn_bwd_dkv_merged_kernel(const unsigned short* __restrict__ q,
     char* ds_head = ds + ((long)b * Hq + hq) * ds_plane * (4 * DS_IMG_BYTES)
                     + ds_lane;
 
-    // The tile body is written as explicit stages so that LDS reads are
-    // issued in groups AHEAD of the MFMAs that consume them (at one wave
-    // per SIMD nothing else hides an LDS round trip; the compiler's own
-    // order was read -> lgkmcnt(0) -> MFMA, one at a time):
-    //   A  the first Q/dO fragment reads of sub-tile sb+1
-    //   B  S/dP chain of sb+1 (MFMA) interleaved with the mask/exp2 pass
-    //      of sb (VALU), plus the remaining fragment reads and the
-    //      transpose reads of sb for dt 0,1
-    //   C  accumulate MFMAs of sb; the dS export behind the first group;
-    //      the transpose reads for dt 2,3 fly under the dt 0,1 MFMAs
-    auto load_frags = [&](int sb, mbf16x8* qf, mbf16x8* of) {
+    // The tile body is a software pipeline over single 32-q sub-tiles,
+    // rotated so that the mask/exp2/pack VALU of sub-tile sb always has
+    // MFMAs under it.  Step sb runs 16 chunks, pinned by sched_barriers;
+    // chunk r holds
+    //   - MFMA r of the S/dP chain of sub-tile sb+1 (even r: S, odd r: dP),
+    //   - MFMA r of the dV/dK accumulation of sub-tile sb-1,
+    //   - the VALU of C-value r of sub-tile sb,
+    // and, in every second chunk, the LDS reads of the next chunk pair
+    // (Q/dO fragments, transpose-read fragments, lse/delta), so that only
+    // a window of them is live.  Carried from
+    // step to step: S/dP of the next sub-tile (ns, ndp) and the P/dS
+    // fragments of the previous one (p0, p1, d0, d1).  The pipeline drains
+    // at the tile boundary: the chain of sub-tile 0 and the accumulation of
+    // the last sub-tile run bare, in front of the tile's one barrier.
+    //
+    // LDS addresses.  For a fixed lane every read of the tile body differs
+    // from a lane constant by a compile-time byte offset: a sub-tile step
+    // adds a multiple of 32 rows, so the (row & 15) << 4 swizzle term does
+    // not move, and the dO image sits TFKV * 256 B behind the Q image.
+    // Twelve addresses (8 d-slices of kimg_frag, 4 d-tiles of nat_tr_frag)
+    // are derived per tile from the opaque copy of the lane id, and every
+    // read is one ds_read at base + immediate.
+    const int hi_t = lane_t >> 5;
+    const int img_off = (int)(qn_c - smem);   // Q image; dO at + DO_OFF
+    constexpr int DO_OFF = TFKV * 256;
+    int a_kf[8], a_tr[4];
+    {
+      // kimg_frag(img, sub, c) = img + sub * 8192 + (kb ^ 32c)
+      const int kb = (lane_t & 31) * 256 +
+                     ((hi_t * 16) ^ ((lane_t & 15) << 4));
       #pragma unroll
-      for (int c = 0; c < 8; ++c) {
-        qf[c] = kimg_frag(qn_c, sb, c);
-        of[c] = kimg_frag(don_c, sb, c);
+      for (int c = 0; c < 8; ++c) a_kf[c] = img_off + (kb ^ (c * 32));
+      // nat_tr_frag(img, ks, dt): low rows at img + ks * 4096 + (tb ^ 64dt),
+      // high rows (+4: swizzle bit 6 flips) at + 1024 + (tb ^ 64(dt ^ 1))
+      const int j = lane_t & 15;
+      const int rl = hi_t * 8 + (j >> 2);
+      const int g16 = ((lane_t >> 4) & 1) * 32 + ((j & 3) >> 1) * 16;
+      const int tb = rl * 256 + ((g16 ^ (rl << 4)) | ((j & 1) * 8));
+      #pragma unroll
+      for (int dt = 0; dt < 4; ++dt) a_tr[dt] = img_off + (tb ^ (dt * 64));
+    }
+    const float* lse_l = &lse_buf[lse_nxt ^ 1][hi_t * 4];
+    const float* del_l = &del_buf[lse_nxt ^ 1][hi_t * 4];
+    // Q (o = 1) / dO (o = 0) fragment of sub-tile sb, d-slice c
+    auto kf_read = [&](int o, int sb, int c)
+        __attribute__((always_inline)) {
+      return *(const mbf16x8*)(smem + a_kf[c] +
+                               ((o ? 0 : DO_OFF) + sb * 8192));
+    };
+    // B fragment of accumulate MFMA i of sub-tile sb, by hardware transpose
+    // read from the natural images (T10).  i = 4 * dt + 2 * k-slice + o:
+    // o = 0 reads dO (for dV += P^T . dO), o = 1 reads Q (dK += dS^T . Q)
+    auto acc_frag = [&](int sb, int i) __attribute__((always_inline)) {
+      const int dt = i >> 2;
+      const int imm = ((i & 1) ? 0 : DO_OFF) +
+                      (2 * sb + ((i >> 1) & 1)) * 4096;
+      short4_v lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
+          (lds_s4p)(smem + a_tr[dt] + imm));
+      short4_v hh = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
+          (lds_s4p)(smem + a_tr[dt ^ 1] + (imm + 1024)));
+      uint2_v ul = __builtin_bit_cast(uint2_v, lo);
+      uint2_v uh = __builtin_bit_cast(uint2_v, hh);
+      uint4_v u = {ul[0], ul[1], uh[0], uh[1]};
+      return __builtin_bit_cast(mbf16x8, u);
+    };
+    // accumulate MFMA i: per accumulator the order is p0 then p1, d0 then
+    // d1, as in the split kernel
+    auto acc_mfma = [&](int i, const mbf16x8& f, const mbf16x8& p0,
+                        const mbf16x8& p1, const mbf16x8& d0,
+                        const mbf16x8& d1) {
+      const int dt = i >> 2;
+      if (i & 1) {
+        acck[dt] = mfma32((i & 2) ? d1 : d0, f, acck[dt]);
+      } else {
+        accv[dt] = mfma32((i & 2) ? p1 : p0, f, accv[dt]);
       }
     };
-    // S[q, k own] and dP[q, k own] (lane owns the k column; q rows via
-    // c_row so the contraction dim of the accumulate MFMAs is the C-row
-    // dim)
-    auto s_chain = [&](const mbf16x8* qf, const mbf16x8* of, f32x16& s_out,
-                       f32x16& dp_out) {
-      f32x16 s = {}, dp = {};
-      #pragma unroll
-      for (int c = 0; c < 8; ++c) {
-        s = mfma32(qf[c], kfrag[c], s);
-        dp = mfma32(of[c], vfrag[c], dp);
+    // export the scaled dS^T sub-tile whole (masked elements are exact
+    // zeros; sub-tiles that start past the last q row are not stored):
+    // 2 x 16 B per lane, 2 KiB contiguous per wave
+    auto export_ds = [&](int sb, const mbf16x8& d0, const mbf16x8& d1) {
+      const int qs0 = q0 + 32 * sb;
+      if (ds_on && sb >= sb0 && qs0 < S) {
+        char* p = ds_head +
+                  (ds_qt_base(qs0 / BLOCK_Q, ds_nqt, causal) * 4 +
+                   ((qs0 / QBLK) & 3)) * DS_IMG_BYTES;
+        *(uint4_v*)p = __builtin_bit_cast(uint4_v, d0);
+        *(uint4_v*)(p + 32) = __builtin_bit_cast(uint4_v, d1);
+        n_ds = 2;
       }
-      s_out = s;
-      dp_out = dp;
     };
 
     if (sb0 < NS) {
@@ -1862,167 +1957,197 @@ attn_bwd_dkv_merged_kernel(const unsigned short* __restrict__ q,
       // dS come out as exact zeros, which leave the accumulators as they
       // are) and only their export is skipped: the tile ends at a barrier
       // behind wave 0, whose sb0 is 0 there, so skipping them would not
-      // end it sooner, and a second entry into the pipelined body costs
-      // the compiler its register allocation.
-      // The pipeline runs over PAIRS of sub-tiles (64 q rows): a rolled
-      // loop over the pairs of a 128-row tile, whose second chain start is
-      // not overlapped — four sub-tiles in one straight line cost more
-      // registers than the wave has.
-      #pragma clang loop unroll(disable)
-      for (int sbase = 0; sbase < NS; sbase += 2) {
-        f32x16 acc_s[2], acc_dp[2];
-        mbf16x8 qf[8], of[8];
-        load_frags(sbase, qf, of);
+      // end it sooner.
+      f32x16 ns, ndp;            // S / dP of the sub-tile the next step owns
+      mbf16x8 p0, p1, d0, d1;    // P / dS fragments of the previous sub-tile
+
+      // one pipeline step; has_prev / has_next say whether an accumulation
+      // and a chain ride under this sub-tile's VALU
+      auto step_body = [&](int sb, auto has_prev, auto has_next,
+                           auto masked)
+          __attribute__((always_inline)) {
+        constexpr bool HP = decltype(has_prev)::value;
+        constexpr bool HN = decltype(has_next)::value;
+        const f32x16 cs = ns, cdp = ndp;
+        mbf16x8 qf[8], of[8];   // chain fragments of sb+1
+        mbf16x8 tf[16];         // accumulate fragments of sb-1
+        f32x4 lv[4], dl[4];
+        // stage A: the reads of the first chunk pair (C-layout rows
+        // 8j + 4*hi + 0..3 of lse/delta are 16 B runs), and the export of
+        // the previous sub-tile's dS
+        if (HN) {
+          qf[0] = kf_read(1, sb + 1, 0);
+          of[0] = kf_read(0, sb + 1, 0);
+        }
+        lv[0] = *(const f32x4*)(lse_l + 32 * sb);
+        dl[0] = *(const f32x4*)(del_l + 32 * sb);
+        if (HP) {
+          tf[0] = acc_frag(sb - 1, 0);
+          tf[1] = acc_frag(sb - 1, 1);
+          export_ds(sb - 1, d0, d1);
+        }
         __builtin_amdgcn_sched_barrier(0);
-        s_chain(qf, of, acc_s[0], acc_dp[0]);
-        #pragma unroll
-        for (int u = 0; u < 2; ++u) {
-          const int sb = sbase + u;
-          const bool nx = u == 0;
-          const f32x16& cs = acc_s[u];
-          const f32x16& cdp = acc_dp[u];
-          // stage A: the first half of the next chain's fragments and this
-          // sub-tile's first lse/delta values (C-layout rows 8j + 4*hi +
-          // 0..3 are 16 B runs); the rest is read inside stage B, eight
-          // chunks (fragments) or four (lse/delta) ahead of its use, so
-          // that only a window of them is live
-          if (nx) {
-            #pragma unroll
-            for (int c = 0; c < 4; ++c) {
-              qf[c] = kimg_frag(qn_c, sb + 1, c);
-              of[c] = kimg_frag(don_c, sb + 1, c);
+
+        // The compiler waits for LDS data with lgkmcnt(0) only, so a wait
+        // drains every read in flight.  The reads therefore go out once
+        // per PAIR of chunks, for the next pair, right behind the pair's
+        // first MFMA — the one place where the wait for this pair's own
+        // operands sits — and have two chunks (four MFMAs) to land.
+        auto pair_reads = [&](int r) __attribute__((always_inline)) {
+          const int n = r + 2;   // first chunk of the next pair
+          if (n < 16) {
+            if (HN) {
+              qf[n >> 1] = kf_read(1, sb + 1, n >> 1);
+              of[n >> 1] = kf_read(0, sb + 1, n >> 1);
+            }
+            if (HP) {
+              tf[n] = acc_frag(sb - 1, n);
+              tf[n + 1] = acc_frag(sb - 1, n + 1);
+            }
+            if (!(n & 3)) {
+              lv[n >> 2] = *(const f32x4*)(lse_l + 32 * sb + 2 * n);
+              dl[n >> 2] = *(const f32x4*)(del_l + 32 * sb + 2 * n);
             }
           }
-          f32x4 lv[4], dl[4];
-          lv[0] = *(const f32x4*)(lse_cur + 32 * sb + (hi ? 4 : 0));
-          dl[0] = *(const f32x4*)(del_cur + 32 * sb + (hi ? 4 : 0));
-          __builtin_amdgcn_sched_barrier(0);
-
-          // stage B, in 16 chunks pinned by sched_barriers: one MFMA of the
-          // next chain, then the mask/exp2 VALU of one C-value, which runs
-          // while the matrix pipe works; the transpose reads for dt 0,1
-          // ride in the second half (in the first sub-tile of a tile the
-          // compiler puts a vmcnt(0) in front of them for the glds pieces
-          // in flight, so they must not come early)
-          const int qs0 = q0 + 32 * sb;
-          // causal masking only bites when SOME (q, k) pair in this
-          // 32q x 32k(own) tile has k > q, i.e. qs0 < kw0 + 32
-          const bool mask_tile = (causal && qs0 < kw0 + 32)
-                                 || (qs0 + 32 > S) || !krow_valid;
-          mbf16x8 p0, p1, d0, d1;
-          mbf16x8 tv[8], tk[8];   // [2 * dt + k-slice]
-          auto stage_b = [&](auto masked) {
-            float cp[16], cd[16];
-            unsigned int pp[8], pd[8];   // packed bf16 pairs of cp / cd
-            f32x16 ns = {}, ndp = {};
-            #pragma unroll
-            for (int r = 0; r < 16; ++r) {
-              if (nx) {
-                if (r & 1) {
-                  ndp = mfma32(of[r >> 1], vfrag[r >> 1], ndp);
-                } else {
-                  ns = mfma32(qf[r >> 1], kfrag[r >> 1], ns);
-                }
-                if (r < 8 && !(r & 1)) {
-                  qf[4 + (r >> 1)] = kimg_frag(qn_c, sb + 1, 4 + (r >> 1));
-                  of[4 + (r >> 1)] = kimg_frag(don_c, sb + 1, 4 + (r >> 1));
-                }
-              }
-              if (r < 12 && !(r & 3)) {
-                const int j = (r >> 2) + 1;
-                lv[j] = *(const f32x4*)(lse_cur + 32 * sb + 8 * j +
-                                        (hi ? 4 : 0));
-                dl[j] = *(const f32x4*)(del_cur + 32 * sb + 8 * j +
-                                        (hi ? 4 : 0));
-              }
-              if (r >= 8) {
-                const int i = r - 8, dt = i >> 2;
-                if (i & 2) {
-                  tk[2 * dt + (i & 1)] =
-                      nat_tr_frag(qn_c, 2 * sb + (i & 1), dt);
-                } else {
-                  tv[2 * dt + (i & 1)] =
-                      nat_tr_frag(don_c, 2 * sb + (i & 1), dt);
-                }
-              }
-              {
-                // the split kernel rounds s*sc2 before it subtracts lse (its
-                // mask select sits between the two): no fused multiply-add
-                // here either, or dS and P differ in the last bit
-                #pragma clang fp contract(off)
-                const int ql = 32 * sb + c_row(r, hi);  // q offset in tile
-                float s2 = cs[r] * sc2;
-                if (decltype(masked)::value) {
-                  const long qg = q0 + ql;
-                  if (qg >= S || !krow_valid || (causal && k_row > qg)) {
-                    s2 = -3.0e38f;
-                  }
-                }
-                const float pr =
-                    __builtin_amdgcn_exp2f(s2 - lv[r >> 2][r & 3]);
-                cp[r] = pr;
-                cd[r] = scale * pr * (cdp[r] - dl[r >> 2][r & 3]);
-              }
-              if (r & 1) {
-                pp[r >> 1] = pack_bf16x2(cp[r - 1], cp[r]);
-                pd[r >> 1] = pack_bf16x2(cd[r - 1], cd[r]);
-              }
+        };
+        float cp[16], cd[16];
+        unsigned int pp[8], pd[8];   // packed bf16 pairs of cp / cd
+        f32x16 s_n = {}, dp_n = {};
+        #pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          if (HN) {
+            if (r & 1) {
+              dp_n = mfma32(of[r >> 1], vfrag[r >> 1], dp_n);
+            } else {
+              s_n = mfma32(qf[r >> 1], kfrag[r >> 1], s_n);
+              __builtin_amdgcn_sched_barrier(0);
+              pair_reads(r);
               __builtin_amdgcn_sched_barrier(0);
             }
-            if (nx) {
-              acc_s[1] = ns;
-              acc_dp[1] = ndp;
+          }
+          if (HP) {
+            acc_mfma(r, tf[r], p0, p1, d0, d1);
+            if (!HN && !(r & 1)) {
+              __builtin_amdgcn_sched_barrier(0);
+              pair_reads(r);
+              __builtin_amdgcn_sched_barrier(0);
             }
-            packed_to_frags_swap(pp, &p0, &p1);
-            packed_to_frags_swap(pd, &d0, &d1);
-          };
-          // the mask_tile gate is a uniform branch around the WHOLE stage,
-          // so the MFMAs and the VALU stay in one block either way
-          if (mask_tile) {
-            stage_b(std::true_type{});
-          } else {
-            stage_b(std::false_type{});
+          }
+          {
+            // the split kernel rounds s*sc2 before it subtracts lse (its
+            // mask select sits between the two): no fused multiply-add
+            // here either, or dS and P differ in the last bit
+            #pragma clang fp contract(off)
+            const int ql = 32 * sb + c_row(r, hi);  // q offset in tile
+            float s2 = cs[r] * sc2;
+            if (decltype(masked)::value) {
+              const long qg = q0 + ql;
+              if (qg >= S || !krow_valid || (causal && k_row > qg)) {
+                s2 = -3.0e38f;
+              }
+            }
+            const float pr =
+                __builtin_amdgcn_exp2f(s2 - lv[r >> 2][r & 3]);
+            cp[r] = pr;
+            cd[r] = scale * pr * (cdp[r] - dl[r >> 2][r & 3]);
+          }
+          // The pack is inline asm, which the compiler's hazard pass does
+          // not look into: packed straight behind its v_exp_f32 it reads
+          // the register before the transcendental unit has written it
+          // (seen on the GPU: the low lanes got the exp2 argument).  So P
+          // is packed one chunk pair late, behind a sched_barrier; dS
+          // comes out of an ordinary multiply and is packed at once.
+          if (r & 1) {
+            if (r >= 3) pp[(r >> 1) - 1] = pack_bf16x2(cp[r - 3], cp[r - 2]);
+            pd[r >> 1] = pack_bf16x2(cd[r - 1], cd[r]);
           }
           __builtin_amdgcn_sched_barrier(0);
+        }
+        if (HN) {
+          ns = s_n;
+          ndp = dp_n;
+        }
+        packed_to_frags_swap(pd, &d0, &d1);
+        __builtin_amdgcn_sched_barrier(0);
+        pp[7] = pack_bf16x2(cp[14], cp[15]);
+        packed_to_frags_swap(pp, &p0, &p1);
+        __builtin_amdgcn_sched_barrier(0);
+      };
+      auto step = [&](int sb, auto has_prev, auto has_next)
+          __attribute__((always_inline)) {
+        const int qs0 = q0 + 32 * sb;
+        // causal masking only bites when SOME (q, k) pair in this
+        // 32q x 32k(own) tile has k > q, i.e. qs0 < kw0 + 32.  The gate is
+        // a wave-uniform branch around the WHOLE step, so the MFMAs and
+        // the VALU stay in one block either way
+        // (kw0 + 32 > S says "some lane's kv row is past S" for the whole
+        // wave: the test must not be per lane, or the lanes would split
+        // over both instances and run the step's MFMAs twice)
+        const bool mask_tile = (causal && qs0 < kw0 + 32)
+                               || (qs0 + 32 > S) || (kw0 + KBLK > S);
+        pin_acc();
+        if (mask_tile) {
+          step_body(sb, has_prev, has_next, std::true_type{});
+        } else {
+          step_body(sb, has_prev, has_next, std::false_type{});
+        }
+      };
 
-          // stage C: dV[k,d] += P^T . dO ; dK[k,d] += dS^T . Q — B fragments
-          // by hardware transpose read from the natural images (T10)
-          accv[0] = mfma32(p0, tv[0], accv[0]);
-          accv[0] = mfma32(p1, tv[1], accv[0]);
-          acck[0] = mfma32(d0, tk[0], acck[0]);
-          acck[0] = mfma32(d1, tk[1], acck[0]);
-          // the transpose reads for dt 2,3 go out first, under the MFMAs
-          // just issued (behind the export they would wait for its stores:
-          // the compiler drains vmcnt in front of them)
-          __builtin_amdgcn_sched_barrier(0);
-          #pragma unroll
-          for (int dt = 2; dt < 4; ++dt) {
-            tv[2 * dt] = nat_tr_frag(don_c, 2 * sb, dt);
-            tv[2 * dt + 1] = nat_tr_frag(don_c, 2 * sb + 1, dt);
-            tk[2 * dt] = nat_tr_frag(qn_c, 2 * sb, dt);
-            tk[2 * dt + 1] = nat_tr_frag(qn_c, 2 * sb + 1, dt);
+      pin_acc();
+      // fill: the chain of sub-tile 0 runs bare.  S[q, k own] and
+      // dP[q, k own]: the lane owns the k column; q rows via c_row so the
+      // contraction dim of the accumulate MFMAs is the C-row dim
+      {
+        mbf16x8 qf[8], of[8];
+        #pragma unroll
+        for (int c = 0; c < 2; ++c) {
+          qf[c] = kf_read(1, 0, c);
+          of[c] = kf_read(0, 0, c);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        f32x16 s = {}, dp = {};
+        #pragma unroll
+        for (int c = 0; c < 8; ++c) {
+          s = mfma32(qf[c], kfrag[c], s);
+          if (!(c & 1) && c + 2 < 8) {
+            // behind the wait of this group of four: the next group's
+            __builtin_amdgcn_sched_barrier(0);
+            #pragma unroll
+            for (int n = c + 2; n < c + 4; ++n) {
+              qf[n] = kf_read(1, 0, n);
+              of[n] = kf_read(0, 0, n);
+            }
+            __builtin_amdgcn_sched_barrier(0);
           }
-          // export the scaled dS^T sub-tile whole (masked elements are exact
-          // zeros; sub-tiles that start past the last q row are not stored):
-          // 2 x 16 B per lane, 2 KiB contiguous per wave, behind the first
-          // accumulate group and the vmcnt(0) the compiler puts in front of
-          // the first transpose read while glds pieces are in flight
+          dp = mfma32(of[c], vfrag[c], dp);
+        }
+        ns = s;
+        ndp = dp;
+        __builtin_amdgcn_sched_barrier(0);
+      }
+      pin_acc();
+      step(0, std::false_type{}, std::true_type{});
+      #pragma unroll
+      for (int sb = 1; sb < NS - 1; ++sb) {
+        step(sb, std::true_type{}, std::true_type{});
+      }
+      step(NS - 1, std::true_type{}, std::false_type{});
+      // drain: the accumulation of the last sub-tile runs bare, its
+      // fragment reads in groups of four, one group ahead
+      {
+        mbf16x8 tf[16];
+        #pragma unroll
+        for (int i = 0; i < 4; ++i) tf[i] = acc_frag(NS - 1, i);
+        export_ds(NS - 1, d0, d1);
+        __builtin_amdgcn_sched_barrier(0);
+        #pragma unroll
+        for (int i = 0; i < 16; ++i) {
+          acc_mfma(i, tf[i], p0, p1, d0, d1);
           __builtin_amdgcn_sched_barrier(0);
-          if (ds_on && sb >= sb0 && qs0 < S) {
-            char* p = ds_head +
-                      (ds_qt_base(qs0 / BLOCK_Q, ds_nqt, causal) * 4 +
-                       ((qs0 / QBLK) & 3)) * DS_IMG_BYTES;
-            *(uint4_v*)p = __builtin_bit_cast(uint4_v, d0);
-            *(uint4_v*)(p + 32) = __builtin_bit_cast(uint4_v, d1);
-            n_ds = 2;
-          }
-          __builtin_amdgcn_sched_barrier(0);
-          #pragma unroll
-          for (int dt = 1; dt < 4; ++dt) {
-            accv[dt] = mfma32(p0, tv[2 * dt], accv[dt]);
-            accv[dt] = mfma32(p1, tv[2 * dt + 1], accv[dt]);
-            acck[dt] = mfma32(d0, tk[2 * dt], acck[dt]);
-            acck[dt] = mfma32(d1, tk[2 * dt + 1], acck[dt]);
+          if (!(i & 3) && i + 4 < 16) {
+            #pragma unroll
+            for (int n = i + 4; n < i + 8; ++n) tf[n] = acc_frag(NS - 1, n);
+            __builtin_amdgcn_sched_barrier(0);
           }
         }
       }
@@ -2047,8 +2172,6 @@ attn_bwd_dkv_merged_kernel(const unsigned short* __restrict__ q,
       // behind lgkmcnt(0) (the lse/delta write above), without the fence
       // of a __syncthreads, which drains vmcnt to 0 by itself
       asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-      lse_cur = lse_buf[lse_nxt];
-      del_cur = del_buf[lse_nxt];
       lse_nxt ^= 1;
       char* tp;
       tp = qn_c; qn_c = qn_n; qn_n = tp;
