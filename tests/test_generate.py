@@ -237,6 +237,31 @@ def test_decode_attention_split_long_cache():
     assert err < 3e-2, err
 
 
+@pytest.mark.gpu
+@pytest.mark.parametrize("B,Hq,Hkv", [(2, 8, 4),     # B*Hq < 512: split
+                                      (8, 64, 8)],   # B*Hq = 512: single pass
+                         ids=["split", "single-pass"])
+def test_decode_attention_length_paths_bit_identical(B, Hq, Hkv):
+    # the host length, the device scalar pos and the per-row [B] pos reach
+    # the same kernel body: same L -> same bits. L = 33 leaves the 16-row
+    # loop a ragged tail and the split chunks unequal.
+    from torchx_amd import ops
+
+    dev = torch.device("cuda:0")
+    torch.manual_seed(11)
+    T, L, D = 48, 33, 128
+    q = torch.randn(B, Hq, D, device=dev, dtype=torch.bfloat16)
+    kc = torch.randn(B, T, Hkv, D, device=dev, dtype=torch.bfloat16)
+    vc = torch.randn(B, T, Hkv, D, device=dev, dtype=torch.bfloat16)
+    o_host = ops.decode_attention(q, kc, vc, L)
+    pos1 = torch.tensor([L - 1], device=dev, dtype=torch.int32)
+    o_scalar = ops.decode_attention_dev(q, kc, vc, pos1)
+    posB = torch.full((B,), L - 1, device=dev, dtype=torch.int32)
+    o_rows = ops.decode_attention_dev(q, kc, vc, posB)
+    assert torch.equal(o_host, o_scalar)
+    assert torch.equal(o_host, o_rows)
+
+
 def test_generate_app_cpu(capsys):
     from torchx_amd.apps import generate_main
 

@@ -76,13 +76,16 @@ def build(force: bool = False, verbose: bool = True) -> Path:
         f"-I{py_inc}",
     ]
 
+    # any header may be included by any source: an object is current only
+    # if it is newer than its source and than every header
+    hdr_mtime = max(h.stat().st_mtime for h in CSRC.glob("*.h"))
     procs = []
     for src in SOURCES:
         obj = build_dir / (src.replace(".", "_") + ".o")
         objs.append(obj)
         src_path = CSRC / src
         if obj.exists() and obj.stat().st_mtime > src_path.stat().st_mtime \
-                and obj.stat().st_mtime > (CSRC / "common.h").stat().st_mtime \
+                and obj.stat().st_mtime > hdr_mtime \
                 and not force:
             continue
         cmd = ["hipcc", "-c", str(src_path), "-o", str(obj)] + common_flags

@@ -12,18 +12,13 @@
 //    fragment packing, defer-max rescale skip), one shfl_xor(32) partner
 //    exchange, no cross-lane LDS reduction.
 //  * KV tiles of 64 rows; K/V arrive by async global_load_lds into
-//    XOR-swizzled natural images; the transposed operand images (V^T /
-//    Q^T / dO^T / K^T) use a granule-ROTATED placement (rot(d) =
-//    (d>>1 ^ d>>4) & 7: reads conflict-free, staging writes ~4-way — a
-//    plain layout measured 36% of wave cycles in LDS bank conflicts) and
-//    are built WAVE-LOCALLY from the just-landed naturals (each wave
-//    transposes the rows it staged, so its own vmcnt(0) orders the read
-//    and ONE barrier per tile publishes everything).
+//    XOR-swizzled natural images; the transposed operands (V^T / Q^T /
+//    dO^T / K^T) are read straight off those images with hardware
+//    transpose reads (nat_tr_frag), so no transposed image is built.
 //  * T1 XCD swizzle: blocks streaming the same (batch, kv-head) tensors
 //    land on one XCD so the stream is L2-resident (the kernels are
 //    otherwise HBM-bound at ~128 FLOP/B).
-//  * Forward block size is 4 waves at every length (the 8-wave variant
-//    stays selectable for re-measurement, see attn_fwd_launch).
+//  * Forward block size is 4 waves at every length.
 //  * paged_prefill_attn_kernel: the 4-wave forward over a block-table KV
 //    cache, for a chunk of query rows behind an already cached prefix;
 //    paged_prefill_attn_ragged_kernel: the same block work over a packed
@@ -110,7 +105,6 @@ __device__ __forceinline__ void cvals_to_frags(const float* p, bool hi,
 
 #define FKV 64                      // kv rows per staged tile
 #define KIMG_BYTES (FKV * 256)      // [64 rows][256 B], byte ^= (row&15)<<4
-#define VIMG_BYTES (HD * FKV * 2)   // V^T [128 d][128 B], byte ^= (d&7)<<4
 #define LOG2E 1.44269504088896340736f
 #define LN2 0.69314718055994530942f
 
@@ -123,34 +117,14 @@ __device__ __forceinline__ mbf16x8 kimg_frag(const char* kimg, int sub, int c) {
   return *(const mbf16x8*)(kimg + row * 256 + byte);
 }
 
-// V^T image: element (d, k) lives at byte
-//   d*128 + ((k>>3 + rot(d)) & 7)*16 + (k&7)*2,   rot(d) = (d>>1 ^ d>>4)&7
-// i.e. the 8 16-B granules of each 128-B d-row are ADD-rotated by a
-// d-keyed amount.  Reads (16 consecutive d per lane group, fixed granule)
-// see 8 distinct rotations x 2 parities -> conflict-free; the transposed
-// staging writes (d = 8g+j, g varying per lane) see 8 granules x 2 r-slots
-// -> ~4-way instead of the 32-way a plain layout gives (which measured as
-// 36% of wave-cycles lost to LDS bank conflicts).
-__device__ __forceinline__ int vrot(int d) {
-  return ((d >> 1) ^ (d >> 4)) & 7;
-}
-
-// V^T fragment: row d = dt*32 + (lane&31), k-slice ks -> 16 B.
-__device__ __forceinline__ mbf16x8 vimg_frag(const char* vimg, int dt, int ks) {
-  const int lane = threadIdx.x & 63;
-  const int d = dt * 32 + (lane & 31);
-  const int g = (ks * 2 + (lane >> 5) + vrot(d)) & 7;
-  return *(const mbf16x8*)(vimg + d * 128 + g * 16);
-}
-
 // ---------------------------------------------------------------------------
-// T10 hardware transpose read: assemble the same fragment a vimg_frag of a
-// transposed image gives — lane holds 8 elements (rows ks*16+(lane>>5)*8+j
+// T10 hardware transpose read: assemble the MFMA fragment of the
+// TRANSPOSED tile — lane holds 8 elements (rows ks*16+(lane>>5)*8+j
 // of the NATURAL 64-row image, at its own column dt*32+(lane&31)) — with
 // two ds_read_tr16_b64 per fragment, straight off the XOR-swizzled natural
-// image.  Kills the explicit LDS transposes (and their images) in the
-// backward kernels.  Per-16-lane-cluster semantics (probe-verified,
-// tools/probe_tr_read.py): lane j addresses the 4-bf16 chunk
+// image, so no kernel builds a transposed LDS image.  Per-16-lane-cluster
+// semantics (probe-verified, tools/probe_tr_read.py): lane j addresses the
+// 4-bf16 chunk
 // (row r0 + (j>>2), cols cbase + 4*(j&3)); lane i receives the 4 rows at
 // column cbase + i, packed low-to-high.
 // ---------------------------------------------------------------------------
@@ -225,37 +199,6 @@ __device__ __forceinline__ void stage_k_glds_at(
   }
 }
 
-// V tile -> registers (4 x b128 per thread); written transposed+swizzled
-// into the LDS V^T image after the barrier.
-__device__ __forceinline__ void load_v_regs(
-    const unsigned short* __restrict__ vb, long kv0, long stride_elems,
-    int S, ushort8 vr[4]) {
-  const int tid = threadIdx.x;
-  #pragma unroll
-  for (int p = 0; p < 4; ++p) {
-    const int c = tid + p * 256;          // 1024 chunks = 64 rows x 16
-    const int r = c >> 4, g = c & 15;     // k row, d granule [8g, 8g+8)
-    long srow = kv0 + r;
-    if (srow >= S) srow = S - 1;
-    vr[p] = *(const ushort8*)(vb + srow * stride_elems + g * 8);
-  }
-}
-
-__device__ __forceinline__ void write_v_tr(const ushort8 vr[4], char* vimg) {
-  const int tid = threadIdx.x;
-  #pragma unroll
-  for (int p = 0; p < 4; ++p) {
-    const int c = tid + p * 256;
-    const int r = c >> 4, g = c & 15;
-    #pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const int d = 8 * g + j;
-      const int gr = ((r >> 3) + vrot(d)) & 7;
-      *(unsigned short*)(vimg + d * 128 + gr * 16 + (r & 7) * 2) = vr[p][j];
-    }
-  }
-}
-
 
 // T1 XCD-aware block swizzle: the dispatcher hands consecutive blockIdx to
 // consecutive XCDs (each with its own 4 MB L2).  Group the G*nqt blocks
@@ -326,54 +269,28 @@ __device__ __forceinline__ bool map_block_fwd_balanced(int B, int Hq, int Hkv,
   return true;
 }
 
-// Build the rot-placed transposed image from a staged swizzled natural
-// image: per thread NCHUNK b128 LDS reads + 8 scalar writes each.  The
-// source tile arrived by glds earlier in the iteration, so the transpose
-// costs an LDS round trip (~50 cyc) instead of a global re-read (~200+).
-template <int NTHREADS>
-__device__ __forceinline__ void lds_nat_to_tr(const char* nat, char* tr_img) {
-  const int tid = threadIdx.x;
+// Forward O epilogue: normalise this lane's q row of O^T and store it as
+// bf16 at `ob` (the row's d = 0), 8 bytes per store.
+__device__ __forceinline__ void fwd_store_o(const f32x16 (&acc_o)[4],
+                                            float l_run, bool hi,
+                                            unsigned short* ob) {
+  const float inv_l = (l_run > 0.f) ? 1.0f / l_run : 0.f;
   #pragma unroll
-  for (int p = 0; p < 1024 / NTHREADS; ++p) {
-    const int c = tid + p * NTHREADS;
-    const int r = c >> 4, g = c & 15;
-    const ushort8 v = *(const ushort8*)(
-        nat + r * 256 + ((g * 16) ^ ((r & 15) << 4)));
+  for (int dt = 0; dt < 4; ++dt) {
     #pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const int d = 8 * g + j;
-      const int gr = ((r >> 3) + vrot(d)) & 7;
-      *(unsigned short*)(tr_img + d * 128 + gr * 16 + (r & 7) * 2) = v[j];
+    for (int g = 0; g < 4; ++g) {
+      // regs 4g..4g+3 are consecutive d: d = dt*32 + 8g + 4*hi + (0..3)
+      bf16x4_raw w;
+      #pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        w[j] = (short)f32_to_bf16(acc_o[dt][4 * g + j] * inv_l);
+      }
+      *(bf16x4_raw*)(ob + dt * 32 + 8 * g + 4 * (hi ? 1 : 0)) = w;
     }
   }
 }
 
-
-
-// Wave-local transpose: wave w transposes the 64/NW rows it glds-staged
-// itself — its own vmcnt(0) orders the read (no pre-barrier needed).
-template <int NW = 4>
-__device__ __forceinline__ void lds_nat_to_tr_own(const char* nat,
-                                                  char* tr_img) {
-  const int wave = threadIdx.x / 64;
-  const int lane = threadIdx.x & 63;
-  #pragma unroll
-  for (int pp = 0; pp < 16 / NW; ++pp) {
-    const int c = wave * (64 * 16 / NW) + pp * 64 + lane;
-    const int r = c >> 4, g = c & 15;
-    const ushort8 v = *(const ushort8*)(
-        nat + r * 256 + ((g * 16) ^ ((r & 15) << 4)));
-    #pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const int d = 8 * g + j;
-      const int gr = ((r >> 3) + vrot(d)) & 7;
-      *(unsigned short*)(tr_img + d * 128 + gr * 16 + (r & 7) * 2) = v[j];
-    }
-  }
-}
-
-template <int NW>
-__global__ void __launch_bounds__(NW * 64, 2)
+__global__ void __launch_bounds__(256, 2)
 attn_fwd_kernel(const unsigned short* __restrict__ q,
                 const unsigned short* __restrict__ k,
                 const unsigned short* __restrict__ v,
@@ -387,7 +304,7 @@ attn_fwd_kernel(const unsigned short* __restrict__ q,
   // build, 64 KiB LDS -> true 2 blocks/CU.
   __shared__ __align__(16) char smem[4 * KIMG_BYTES];
 
-  const int BQ = NW * QBLK;
+  const int BQ = BLOCK_Q;
   const int nqt = (S + BQ - 1) / BQ;
   const int G = Hq / Hkv;
   int b, hq, qt;
@@ -440,8 +357,8 @@ attn_fwd_kernel(const unsigned short* __restrict__ q,
   char* vnxt = smem + 3 * KIMG_BYTES;    // V natural nxt
 
   // prologue: glds K0 + V0 natural
-  stage_k_glds<NW>(kb, 0, kv_seq_stride, S, k0);
-  stage_k_glds<NW>(vb, 0, kv_seq_stride, S, vcur);
+  stage_k_glds<4>(kb, 0, kv_seq_stride, S, k0);
+  stage_k_glds<4>(vb, 0, kv_seq_stride, S, vcur);
   asm volatile("s_waitcnt vmcnt(0)");
   __syncthreads();
 
@@ -451,8 +368,8 @@ attn_fwd_kernel(const unsigned short* __restrict__ q,
     if (has_next) {
       // issue next K/V glds BEFORE compute (T14: their latency hides
       // under this tile's MFMAs; the stream is L2-resident anyway)
-      stage_k_glds<NW>(kb, kv0 + FKV, kv_seq_stride, S, k1);
-      stage_k_glds<NW>(vb, kv0 + FKV, kv_seq_stride, S, vnxt);
+      stage_k_glds<4>(kb, kv0 + FKV, kv_seq_stride, S, k1);
+      stage_k_glds<4>(vb, kv0 + FKV, kv_seq_stride, S, vnxt);
     }
 
     const bool needed = wave_active && (!causal || kv0 <= qw_max);
@@ -544,22 +461,7 @@ attn_fwd_kernel(const unsigned short* __restrict__ q,
 
   if (!wave_active || q_row >= S) return;
 
-  const float inv_l = (l_run > 0.f) ? 1.0f / l_run : 0.f;
-  unsigned short* ob =
-      o + (((long)b * S + q_row) * Hq + hq) * HD;  // o is dense BSHD
-  #pragma unroll
-  for (int dt = 0; dt < 4; ++dt) {
-    #pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      // regs 4g..4g+3 are consecutive d: d = dt*32 + 8g + 4*hi + (0..3)
-      bf16x4_raw w;
-      #pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        w[j] = (short)f32_to_bf16(acc_o[dt][4 * g + j] * inv_l);
-      }
-      *(bf16x4_raw*)(ob + dt * 32 + 8 * g + 4 * (hi ? 1 : 0)) = w;
-    }
-  }
+  fwd_store_o(acc_o, l_run, hi, o + (((long)b * S + q_row) * Hq + hq) * HD);
   if (!hi) {
     // lse stays in the natural-log domain for the backward kernels
     lse[((long)b * Hq + hq) * S + q_row] = (m_run + __log2f(l_run)) * LN2;
@@ -578,7 +480,7 @@ attn_fwd_kernel(const unsigned short* __restrict__ q,
 //   ctx          int32 [B]
 //   o            [B, S, Hq, 128] bf16       (no lse: inference only)
 //
-// This is attn_fwd_kernel<4> (causal) with two changes. (1) The staging
+// This is attn_fwd_kernel (causal) with two changes. (1) The staging
 // source row goes through the table. A wave stages the 16 consecutive,
 // 16-aligned logical rows [kv0 + 16w, +16) of a tile, which lie in ONE
 // page for every P >= 16, so a tile costs each lane one table entry; rows
@@ -591,7 +493,7 @@ attn_fwd_kernel(const unsigned short* __restrict__ q,
 // The LDS images, the tile sequence, the MFMA order and the softmax are
 // the dense kernel's expressions in the dense kernel's order. Hence, for
 // ctx[b] % 128 == 0, row i of the output is bit-identical to row
-// ctx[b] + i of attn_fwd_kernel<4> (causal) over the gathered dense
+// ctx[b] + i of attn_fwd_kernel (causal) over the gathered dense
 // sequence of length ctx[b] + S: the block holds the same 128 q rows, its
 // waves the same 32, and every wave walks the same tiles. For any other
 // ctx the grouping of q rows into waves differs, the __all of the
@@ -818,21 +720,7 @@ __device__ __forceinline__ void paged_prefill_tile(
 
   if (!wave_active || q_row >= S) return;
 
-  const float inv_l = (l_run > 0.f) ? 1.0f / l_run : 0.f;
-  unsigned short* orow = ob + q_row * q_seq_stride;
-  #pragma unroll
-  for (int dt = 0; dt < 4; ++dt) {
-    #pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      // regs 4g..4g+3 are consecutive d: d = dt*32 + 8g + 4*hi + (0..3)
-      bf16x4_raw w;
-      #pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        w[j] = (short)f32_to_bf16(acc_o[dt][4 * g + j] * inv_l);
-      }
-      *(bf16x4_raw*)(orow + dt * 32 + 8 * g + 4 * (hi ? 1 : 0)) = w;
-    }
-  }
+  fwd_store_o(acc_o, l_run, hi, ob + q_row * q_seq_stride);
 }
 
 __global__ void __launch_bounds__(256, 2)
@@ -1340,28 +1228,6 @@ __device__ __forceinline__ void stage_k_glds8(
 // B-op), dO^T (dV accumulate B-op) — double-buffered in 128 KiB LDS, one
 // barrier per tile.
 // ---------------------------------------------------------------------------
-
-// Wave-local variant for 8-wave blocks: wave w transposes ONLY the 8
-// rows it glds-staged itself ([8w, 8w+8)), so its own s_waitcnt vmcnt(0)
-// is the only ordering needed before the transpose — no pre-barrier.
-__device__ __forceinline__ void lds_nat_to_tr_own8(const char* nat,
-                                                   char* tr_img) {
-  const int wave = threadIdx.x / 64;
-  const int lane = threadIdx.x & 63;
-  #pragma unroll
-  for (int pp = 0; pp < 2; ++pp) {
-    const int c = wave * 128 + pp * 64 + lane;
-    const int r = c >> 4, g = c & 15;
-    const ushort8 v = *(const ushort8*)(
-        nat + r * 256 + ((g * 16) ^ ((r & 15) << 4)));
-    #pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const int d = 8 * g + j;
-      const int gr = ((r >> 3) + vrot(d)) & 7;
-      *(unsigned short*)(tr_img + d * 128 + gr * 16 + (r & 7) * 2) = v[j];
-    }
-  }
-}
 
 template <int TFKV>
 __global__ void __launch_bounds__(512, 2)
@@ -2220,7 +2086,7 @@ attn_bwd_dkv_merged_kernel(const unsigned short* __restrict__ q,
 // ---------------------------------------------------------------------------
 // Launchers
 // ---------------------------------------------------------------------------
-// Block map of attn_fwd_kernel<4>: 0 = map_block_fwd ("legacy"),
+// Block map of attn_fwd_kernel: 0 = map_block_fwd ("legacy"),
 // 1 = balanced (unit-adjacent, heaviest first), 2 = unit-adjacent with
 // tiles ascending.  Initial value from TORCHX_AMD_FWD_MAP, read once; the
 // setter switches it at run time so one process can run all of them.
@@ -2246,38 +2112,19 @@ extern "C" void attn_fwd_launch(const void* q, const void* k, const void* v,
                                 void* o, void* lse, int B, int S, int Hq,
                                 int Hkv, float scale, int causal,
                                 long q_rs, long kv_rs, hipStream_t stream) {
-  // Post-T10 the 4-wave block wins at EVERY length (S=4096: 618 vs 558
-  // TF/s; S=8192: 706 vs 648 — the pre-T10 dispatch sent S>=8192 to the
-  // 8-wave variant, which lost its edge once the V^T build disappeared
-  // and the 4-wave kernel fit 2 blocks/CU).  TORCHX_AMD_FWD_8WAVE=1
-  // forces the 8-wave path for re-measurement.
-  static int fwd8 = -1;
-  if (fwd8 < 0) {
-    const char* e = getenv("TORCHX_AMD_FWD_8WAVE");
-    fwd8 = (e && atoi(e)) ? 1 : 0;
+  const int nqt = (S + BLOCK_Q - 1) / BLOCK_Q;
+  const int map = attn_fwd_map_get();
+  // the balanced maps' fallback rounds the grid up to whole rounds of 8
+  // units of G blocks (map_block_fwd_balanced)
+  long grid = (long)B * Hq * nqt;
+  if (map != 0 && ((B * Hkv) & 7) != 0) {
+    grid = ((long)B * Hkv * nqt + 7) / 8 * 8 * (Hq / Hkv);
   }
-  if (fwd8 == 1) {
-    const int nqt = (S + 8 * QBLK - 1) / (8 * QBLK);
-    hipLaunchKernelGGL((attn_fwd_kernel<8>), dim3(B * Hq * nqt), dim3(512),
-                       0, stream, (const unsigned short*)q,
-                       (const unsigned short*)k, (const unsigned short*)v,
-                       (unsigned short*)o, (float*)lse, B, S, Hq, Hkv,
-                       scale, causal, q_rs, kv_rs, 0);
-  } else {
-    const int nqt = (S + 4 * QBLK - 1) / (4 * QBLK);
-    const int map = attn_fwd_map_get();
-    // the balanced maps' fallback rounds the grid up to whole rounds of 8
-    // units of G blocks (map_block_fwd_balanced)
-    long grid = (long)B * Hq * nqt;
-    if (map != 0 && ((B * Hkv) & 7) != 0) {
-      grid = ((long)B * Hkv * nqt + 7) / 8 * 8 * (Hq / Hkv);
-    }
-    hipLaunchKernelGGL((attn_fwd_kernel<4>), dim3((unsigned)grid), dim3(256),
-                       0, stream, (const unsigned short*)q,
-                       (const unsigned short*)k, (const unsigned short*)v,
-                       (unsigned short*)o, (float*)lse, B, S, Hq, Hkv,
-                       scale, causal, q_rs, kv_rs, map);
-  }
+  hipLaunchKernelGGL(attn_fwd_kernel, dim3((unsigned)grid), dim3(256), 0,
+                     stream, (const unsigned short*)q,
+                     (const unsigned short*)k, (const unsigned short*)v,
+                     (unsigned short*)o, (float*)lse, B, S, Hq, Hkv, scale,
+                     causal, q_rs, kv_rs, map);
 }
 
 extern "C" void paged_prefill_attn_launch(
@@ -2350,42 +2197,23 @@ extern "C" void attn_bwd_launch(const void* q, const void* k, const void* v,
     const char* e = getenv("TORCHX_AMD_DKV_FKV");
     dkv_fkv = (e && atoi(e) == 64) ? 64 : 128;
   }
+  // the merged and the split (8-wave) kernels take the same arguments
+  auto launch_dkv = [&](auto kernel, int threads) {
+    hipLaunchKernelGGL(kernel, dim3(B * Hkv * nkt), dim3(threads), 0, stream,
+                       (const unsigned short*)q, (const unsigned short*)k,
+                       (const unsigned short*)v, (const unsigned short*)dout,
+                       (const float*)lse, (const float*)delta,
+                       (unsigned short*)dk, (unsigned short*)dv, (char*)ds,
+                       B, S, Hq, Hkv, scale, causal, q_rs, kv_rs, dout_rs,
+                       dqkv_kv_rs);
+  };
+  const bool dkv128 = dkv_fkv == 128 && S % 128 == 0;
   if (attn_bwd_dkv_impl_get() == 1) {
-    if (dkv_fkv == 128 && S % 128 == 0) {
-      hipLaunchKernelGGL((attn_bwd_dkv_merged_kernel<128>),
-                         dim3(B * Hkv * nkt), dim3(256), 0, stream,
-                         (const unsigned short*)q, (const unsigned short*)k,
-                         (const unsigned short*)v,
-                         (const unsigned short*)dout, (const float*)lse,
-                         (const float*)delta, (unsigned short*)dk,
-                         (unsigned short*)dv, (char*)ds, B, S, Hq, Hkv,
-                         scale, causal, q_rs, kv_rs, dout_rs, dqkv_kv_rs);
-    } else {
-      hipLaunchKernelGGL((attn_bwd_dkv_merged_kernel<64>),
-                         dim3(B * Hkv * nkt), dim3(256), 0, stream,
-                         (const unsigned short*)q, (const unsigned short*)k,
-                         (const unsigned short*)v,
-                         (const unsigned short*)dout, (const float*)lse,
-                         (const float*)delta, (unsigned short*)dk,
-                         (unsigned short*)dv, (char*)ds, B, S, Hq, Hkv,
-                         scale, causal, q_rs, kv_rs, dout_rs, dqkv_kv_rs);
-    }
-  } else if (dkv_fkv == 128 && S % 128 == 0) {
-    hipLaunchKernelGGL((attn_bwd_dkv_kernel<128>), dim3(B * Hkv * nkt),
-                       dim3(512), 0, stream, (const unsigned short*)q,
-                       (const unsigned short*)k, (const unsigned short*)v,
-                       (const unsigned short*)dout, (const float*)lse,
-                       (const float*)delta, (unsigned short*)dk,
-                       (unsigned short*)dv, (char*)ds, B, S, Hq, Hkv,
-                       scale, causal, q_rs, kv_rs, dout_rs, dqkv_kv_rs);
+    if (dkv128) launch_dkv(attn_bwd_dkv_merged_kernel<128>, 256);
+    else launch_dkv(attn_bwd_dkv_merged_kernel<64>, 256);
   } else {
-    hipLaunchKernelGGL((attn_bwd_dkv_kernel<64>), dim3(B * Hkv * nkt),
-                       dim3(512), 0, stream, (const unsigned short*)q,
-                       (const unsigned short*)k, (const unsigned short*)v,
-                       (const unsigned short*)dout, (const float*)lse,
-                       (const float*)delta, (unsigned short*)dk,
-                       (unsigned short*)dv, (char*)ds, B, S, Hq, Hkv,
-                       scale, causal, q_rs, kv_rs, dout_rs, dqkv_kv_rs);
+    if (dkv128) launch_dkv(attn_bwd_dkv_kernel<128>, 512);
+    else launch_dkv(attn_bwd_dkv_kernel<64>, 512);
   }
   const int nqt = (S + BLOCK_Q - 1) / BLOCK_Q;
   if (ds != nullptr) {
@@ -2408,19 +2236,14 @@ extern "C" void attn_bwd_launch(const void* q, const void* k, const void* v,
     const char* e = getenv("TORCHX_AMD_DQ_FKV");
     dq_fkv = (e && atoi(e) == 128) ? 128 : 64;
   }
-  if (dq_fkv == 128 && S % 128 == 0) {
-    hipLaunchKernelGGL((attn_bwd_dq_kernel<128>), dim3(B * Hq * nqt),
-                       dim3(256), 0, stream, (const unsigned short*)q,
-                       (const unsigned short*)k, (const unsigned short*)v,
-                       (const unsigned short*)dout, (const float*)lse,
-                       (const float*)delta, (unsigned short*)dq, B, S, Hq,
-                       Hkv, scale, causal, q_rs, kv_rs, dqkv_q_rs);
-  } else {
-    hipLaunchKernelGGL((attn_bwd_dq_kernel<64>), dim3(B * Hq * nqt),
-                       dim3(256), 0, stream, (const unsigned short*)q,
-                       (const unsigned short*)k, (const unsigned short*)v,
-                       (const unsigned short*)dout, (const float*)lse,
-                       (const float*)delta, (unsigned short*)dq, B, S, Hq,
-                       Hkv, scale, causal, q_rs, kv_rs, dqkv_q_rs);
-  }
+  auto launch_dq = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, dim3(B * Hq * nqt), dim3(256), 0, stream,
+                       (const unsigned short*)q, (const unsigned short*)k,
+                       (const unsigned short*)v, (const unsigned short*)dout,
+                       (const float*)lse, (const float*)delta,
+                       (unsigned short*)dq, B, S, Hq, Hkv, scale, causal,
+                       q_rs, kv_rs, dqkv_q_rs);
+  };
+  if (dq_fkv == 128 && S % 128 == 0) launch_dq(attn_bwd_dq_kernel<128>);
+  else launch_dq(attn_bwd_dq_kernel<64>);
 }

@@ -482,6 +482,28 @@ at::Tensor transpose_bf16(at::Tensor x) {
 }
 
 // ---- decode attention -----------------------------------------------------
+// Split count of the flash-decode variants for q [B, Hq, 128] (enough
+// blocks to fill the chip, at most 16 slices) and the f32 scratch of the
+// partials; split == 1 is the single-pass kernel and needs no scratch.
+struct DecodeSplit {
+  int split;
+  at::Tensor ml, oacc;  // [B*Hq, split, 2], [B*Hq, split, 128]
+  void* mlp = nullptr;
+  void* oaccp = nullptr;
+};
+
+static DecodeSplit decode_split(const at::Tensor& q) {
+  const long BHq = q.size(0) * q.size(1);
+  DecodeSplit sp{(int)std::max(1L, std::min(16L, 512 / BHq))};
+  if (sp.split > 1) {
+    sp.ml = at::empty({BHq * sp.split * 2}, q.options().dtype(at::kFloat));
+    sp.oacc = at::empty({BHq * sp.split * 128}, q.options().dtype(at::kFloat));
+    sp.mlp = sp.ml.data_ptr();
+    sp.oaccp = sp.oacc.data_ptr();
+  }
+  return sp;
+}
+
 // q [B, Hq, 128] bf16; k/v caches [B, T, Hkv, 128] bf16; first L rows
 // valid. Returns o [B, Hq, 128].
 at::Tensor decode_attn(at::Tensor q, at::Tensor kc, at::Tensor vc, long L,
@@ -495,15 +517,11 @@ at::Tensor decode_attn(at::Tensor q, at::Tensor kc, at::Tensor vc, long L,
   TORCH_CHECK(L >= 1 && L <= T, "invalid cache length");
   TORCH_CHECK(Hq % Hkv == 0, "GQA group mismatch");
   auto o = at::empty_like(q);
-  const int split = std::max(1, std::min(16, 512 / (B * Hq)));
-  if (split > 1) {
-    auto ml = at::empty({(long)B * Hq * split * 2},
-                        q.options().dtype(at::kFloat));
-    auto oacc = at::empty({(long)B * Hq * split * 128},
-                          q.options().dtype(at::kFloat));
+  const DecodeSplit sp = decode_split(q);
+  if (sp.split > 1) {
     decode_attn_split_launch(q.data_ptr(), kc.data_ptr(), vc.data_ptr(),
-                             ml.data_ptr(), oacc.data_ptr(), o.data_ptr(),
-                             nullptr, B, Hq, Hkv, T, (int)L, split, 0,
+                             sp.mlp, sp.oaccp, o.data_ptr(), nullptr, B, Hq,
+                             Hkv, T, (int)L, sp.split, 0,
                              (float)scale, cur_stream());
   } else {
     decode_attn_launch(q.data_ptr(), kc.data_ptr(), vc.data_ptr(),
@@ -527,16 +545,12 @@ at::Tensor decode_attn_dev(at::Tensor q, at::Tensor kc, at::Tensor vc,
   const int per_row = pos.numel() == B && B > 1 ? 1 : 0;
   const int T = kc.size(1), Hkv = kc.size(2);
   auto o = at::empty_like(q);
-  const int split = std::max(1, std::min(16, 512 / (B * Hq)));
-  if (split > 1) {
-    auto ml = at::empty({(long)B * Hq * split * 2},
-                        q.options().dtype(at::kFloat));
-    auto oacc = at::empty({(long)B * Hq * split * 128},
-                          q.options().dtype(at::kFloat));
+  const DecodeSplit sp = decode_split(q);
+  if (sp.split > 1) {
     decode_attn_split_launch(q.data_ptr(), kc.data_ptr(), vc.data_ptr(),
-                             ml.data_ptr(), oacc.data_ptr(), o.data_ptr(),
-                             pos.data_ptr(), B, Hq, Hkv, T, 0, split,
-                             per_row, (float)scale, cur_stream());
+                             sp.mlp, sp.oaccp, o.data_ptr(), pos.data_ptr(),
+                             B, Hq, Hkv, T, 0, sp.split, per_row,
+                             (float)scale, cur_stream());
   } else {
     decode_attn_launch(q.data_ptr(), kc.data_ptr(), vc.data_ptr(),
                        o.data_ptr(), pos.data_ptr(), B, Hq, Hkv, T, 0,
@@ -660,22 +674,11 @@ at::Tensor paged_decode_attn(at::Tensor q, at::Tensor kpool,
   const int M = bt.size(1);
   TORCH_CHECK(Hq % Hkv == 0, "GQA group mismatch");
   auto o = at::empty_like(q);
-  const int split = std::max(1, std::min(16, 512 / (B * Hq)));
-  at::Tensor ml, oacc;
-  void* mlp = nullptr;
-  void* oaccp = nullptr;
-  if (split > 1) {
-    ml = at::empty({(long)B * Hq * split * 2},
-                   q.options().dtype(at::kFloat));
-    oacc = at::empty({(long)B * Hq * split * 128},
-                     q.options().dtype(at::kFloat));
-    mlp = ml.data_ptr();
-    oaccp = oacc.data_ptr();
-  }
+  const DecodeSplit sp = decode_split(q);
   paged_decode_attn_launch(q.data_ptr(), kpool.data_ptr(), vpool.data_ptr(),
-                           mlp, oaccp, o.data_ptr(), bt.data_ptr(),
+                           sp.mlp, sp.oaccp, o.data_ptr(), bt.data_ptr(),
                            pos.data_ptr(), B, Hq, Hkv, num_pages, logP, M,
-                           split, (float)scale, cur_stream());
+                           sp.split, (float)scale, cur_stream());
   return o;
 }
 

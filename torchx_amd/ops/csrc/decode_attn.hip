@@ -1,18 +1,28 @@
-// Single-position (decode) attention over a KV cache, bf16, GQA,
+// Single-position (decode) attention over a dense KV cache, bf16, GQA,
 // HD = 128 — the serving-side counterpart of the training flash kernels.
 //
 //   o[b,hq,:] = softmax(scale * q[b,hq,:] . K[b,:L,hkv,:]^T) . V[b,:L,hkv,:]
 //
-// One 256-thread block per (b, hq). Work split: 16 lanes per cached row
-// (16 x 8 d = 128, ushort8 loads), so a wave covers 4 rows per iteration
-// and the block 16; each wave keeps its OWN online-softmax state (m, l,
-// 8-float o partial per lane) over its rows — flash-decode style — and
-// the four waves merge through LDS once at the end (one barrier).
-// HBM-bound by the K/V cache stream (L x 512 B per (b, hkv), shared by
-// the GQA group via L2).
-#include "common.h"
+// The block body (row loop, online softmax, LDS combine) is
+// decode_attn_block in decode_core.h; the kernels here give it the dense
+// row source and an epilogue. HBM-bound by the K/V cache stream
+// (L x 512 B per (b, hkv), shared by the GQA group via L2).
+#include "decode_core.h"
 
-#define HD 128
+// L from the host, or len + 1 from a device int32: a scalar, or [B] with
+// per_row (ragged / continuous batching)
+__device__ __forceinline__ int dense_len(const int* __restrict__ len_dev,
+                                         int per_row, int b, int L_host) {
+  return len_dev ? (len_dev[per_row ? b : 0] + 1) : L_host;
+}
+
+__device__ __forceinline__ DenseRows dense_rows(
+    const unsigned short* __restrict__ kc,  // [B, T, Hkv, 128]
+    const unsigned short* __restrict__ vc, int b, int hkv, int Hkv, int T) {
+  const long row_stride = (long)Hkv * HD;
+  const long base = (long)b * T * row_stride + (long)hkv * HD;
+  return DenseRows{kc + base, vc + base, row_stride};
+}
 
 __global__ void __launch_bounds__(256)
 decode_attn_kernel(const unsigned short* __restrict__ q,   // [B, Hq, 128]
@@ -24,95 +34,10 @@ decode_attn_kernel(const unsigned short* __restrict__ q,   // [B, Hq, 128]
                    float scale) {
   const int b = blockIdx.x / Hq;
   const int hq = blockIdx.x % Hq;
-  // per_row: len_dev is [B] (ragged / continuous batching); else a scalar
-  const int L = len_dev ? (len_dev[per_row ? b : 0] + 1) : L_host;
-  const int hkv = hq / (Hq / Hkv);
-
-  const int wave = threadIdx.x / 64;
-  const int lane = threadIdx.x & 63;
-  const int tsub = lane >> 4;        // wave's row slot 0..3
-  const int dchunk = (lane & 15) * 8;  // this lane's 8 d's
-
-  // q fragment for this lane's d-chunk (f32)
-  const unsigned short* qp = q + ((long)b * Hq + hq) * HD + dchunk;
-  float qv[8];
-  {
-    ushort8 v = *(const ushort8*)qp;
-    #pragma unroll
-    for (int j = 0; j < 8; ++j) qv[j] = bf16_to_f32(v[j]) * scale;
-  }
-
-  const long row_stride = (long)Hkv * HD;
-  const unsigned short* kb = kc + (long)b * T * row_stride + (long)hkv * HD;
-  const unsigned short* vb = vc + (long)b * T * row_stride + (long)hkv * HD;
-
-  float m_run = -3.0e38f, l_run = 0.f;
-  float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-
-  // rows: wave w owns t = 16*i + 4*w + tsub
-  for (int t = 4 * wave + tsub; t < L; t += 16) {
-    const unsigned short* kr = kb + (long)t * row_stride + dchunk;
-    ushort8 kv8 = *(const ushort8*)kr;
-    float s = 0.f;
-    #pragma unroll
-    for (int j = 0; j < 8; ++j) s = fmaf(qv[j], bf16_to_f32(kv8[j]), s);
-    // reduce the 16-lane group -> every lane of the group has the score
-    #pragma unroll
-    for (int off = 8; off >= 1; off >>= 1) {
-      s += __shfl_xor(s, off, 16);
-    }
-    // online softmax (wave-local state; all 16 lanes of the group agree)
-    const float m_new = fmaxf(m_run, s);
-    const float alpha = __builtin_amdgcn_exp2f(
-        1.44269504f * (m_run - m_new));
-    const float p = __builtin_amdgcn_exp2f(1.44269504f * (s - m_new));
-    l_run = l_run * alpha + p;
-    const unsigned short* vr = vb + (long)t * row_stride + dchunk;
-    ushort8 vv8 = *(const ushort8*)vr;
-    #pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      acc[j] = fmaf(acc[j], alpha, p * bf16_to_f32(vv8[j]));
-    }
-    m_run = m_new;
-  }
-
-  // combine the 4 row-slots of each wave, then the 4 waves: 16 partial
-  // (m, l, o[128]) states -> LDS, block-combined by wave 0
-  __shared__ float sm[16], sl[16], so[16][128];
-  const int slot = wave * 4 + tsub;
-  if ((lane & 15) == 0) {
-    sm[slot] = m_run;
-    sl[slot] = l_run;
-  }
-  #pragma unroll
-  for (int j = 0; j < 8; ++j) so[slot][dchunk + j] = acc[j];
-  __syncthreads();
-
-  if (wave == 0) {
-    // lane group 0..15 handles d-chunk as before; combine 16 slots
-    float m_t = -3.0e38f;
-    #pragma unroll
-    for (int i = 0; i < 16; ++i) m_t = fmaxf(m_t, sm[i]);
-    float l_t = 0.f;
-    float out[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    #pragma unroll
-    for (int i = 0; i < 16; ++i) {
-      const float w = __builtin_amdgcn_exp2f(1.44269504f * (sm[i] - m_t));
-      l_t += sl[i] * w;
-      #pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        out[j] = fmaf(so[i][dchunk + j], w, out[j]);
-      }
-    }
-    const float inv = (l_t > 0.f) ? 1.0f / l_t : 0.f;
-    if (tsub == 0) {  // 16 lanes cover all 128 d
-      unsigned short* op = o + ((long)b * Hq + hq) * HD + dchunk;
-      ushort8 ov;
-      #pragma unroll
-      for (int j = 0; j < 8; ++j) ov[j] = f32_to_bf16(out[j] * inv);
-      *(ushort8*)op = ov;
-    }
-  }
+  const int L = dense_len(len_dev, per_row, b, L_host);
+  const long bq = (long)b * Hq + hq;
+  decode_attn_block(q + bq * HD, dense_rows(kc, vc, b, hq / (Hq / Hkv), Hkv, T),
+                    0, L, scale, StoreOutput{o + bq * HD});
 }
 
 extern "C" void decode_attn_launch(const void* q, const void* kc,
@@ -127,11 +52,11 @@ extern "C" void decode_attn_launch(const void* q, const void* kc,
 }
 
 // Fused decode-side rope + cache append: consumes the packed wqkv output
-// [B, (Hq+2*Hkv)*128] for ONE position, ropes q and k (half-split pairing,
-// same convention as rope_fwdbwd_kernel), writes the roped k and the raw v
-// into the caches at row `pos`, and emits q contiguous [B, Hq, 128] for
-// decode_attn. Replaces ~6 tiny kernels (2x rope, 2x index_copy, split
-// copies) per layer per token; one wave per head, latency-floor bound.
+// [B, (Hq+2*Hkv)*128] for ONE position, ropes q and k, writes the roped k
+// and the raw v into the caches at row `pos`, and emits q contiguous
+// [B, Hq, 128] for decode_attn (decode_rope_append in decode_core.h).
+// Replaces ~6 tiny kernels (2x rope, 2x index_copy, split copies) per layer
+// per token; one wave per head, latency-floor bound.
 // `pos` comes from the host (eager) or a device int32 scalar (hipGraph).
 __global__ void __launch_bounds__(64)
 decode_rope_cache_kernel(const unsigned short* __restrict__ qkv,
@@ -147,26 +72,8 @@ decode_rope_cache_kernel(const unsigned short* __restrict__ qkv,
   const int b = blockIdx.x / nh;
   const int h = blockIdx.x % nh;
   const int pos = pos_dev ? pos_dev[per_row ? b : 0] : pos_host;
-  const int lane = threadIdx.x;  // 0..63: one rotation pair (lane, lane+64)
-  const unsigned short* src = qkv + ((long)b * nh + h) * HD;
-  if (h < Hq + Hkv) {  // q or k head: rotate
-    const float x1 = bf16_to_f32(src[lane]);
-    const float x2 = bf16_to_f32(src[lane + 64]);
-    const float c = cos_t[(long)pos * 64 + lane];
-    const float s = sin_t[(long)pos * 64 + lane];
-    const unsigned short y1 = f32_to_bf16(fmaf(x1, c, -s * x2));
-    const unsigned short y2 = f32_to_bf16(fmaf(x2, c, s * x1));
-    unsigned short* dst =
-        (h < Hq) ? qout + ((long)b * Hq + h) * HD
-                 : kc + (((long)b * T + pos) * Hkv + (h - Hq)) * HD;
-    dst[lane] = y1;
-    dst[lane + 64] = y2;
-  } else {  // v head: plain copy into the cache
-    unsigned short* dst =
-        vc + (((long)b * T + pos) * Hkv + (h - Hq - Hkv)) * HD;
-    dst[lane] = src[lane];
-    dst[lane + 64] = src[lane + 64];
-  }
+  decode_rope_append(qkv, qout, kc, vc, cos_t, sin_t, b, h, Hq, Hkv, pos,
+                     (long)b * T + pos);
 }
 
 extern "C" void decode_rope_cache_launch(const void* qkv, void* qout,
@@ -202,86 +109,15 @@ decode_attn_split_kernel(const unsigned short* __restrict__ q,
   const int bq = blockIdx.x;
   const int b = bq / Hq;
   const int hq = bq % Hq;
-  const int L = len_dev ? (len_dev[per_row ? b : 0] + 1) : L_host;
-  const int hkv = hq / (Hq / Hkv);
+  const int L = dense_len(len_dev, per_row, b, L_host);
   const int split = gridDim.y;
   const int chunk = (L + split - 1) / split;
   const int t0 = blockIdx.y * chunk;
   const int t1 = min(L, t0 + chunk);
-
-  const int wave = threadIdx.x / 64;
-  const int lane = threadIdx.x & 63;
-  const int tsub = lane >> 4;
-  const int dchunk = (lane & 15) * 8;
-
-  const unsigned short* qp = q + ((long)b * Hq + hq) * HD + dchunk;
-  float qv[8];
-  {
-    ushort8 v = *(const ushort8*)qp;
-    #pragma unroll
-    for (int j = 0; j < 8; ++j) qv[j] = bf16_to_f32(v[j]) * scale;
-  }
-
-  const long row_stride = (long)Hkv * HD;
-  const unsigned short* kb = kc + (long)b * T * row_stride + (long)hkv * HD;
-  const unsigned short* vb = vc + (long)b * T * row_stride + (long)hkv * HD;
-
-  float m_run = -3.0e38f, l_run = 0.f;
-  float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  for (int t = t0 + 4 * wave + tsub; t < t1; t += 16) {
-    const unsigned short* kr = kb + (long)t * row_stride + dchunk;
-    ushort8 kv8 = *(const ushort8*)kr;
-    float s = 0.f;
-    #pragma unroll
-    for (int j = 0; j < 8; ++j) s = fmaf(qv[j], bf16_to_f32(kv8[j]), s);
-    #pragma unroll
-    for (int off = 8; off >= 1; off >>= 1) s += __shfl_xor(s, off, 16);
-    const float m_new = fmaxf(m_run, s);
-    const float alpha = __builtin_amdgcn_exp2f(1.44269504f * (m_run - m_new));
-    const float p = __builtin_amdgcn_exp2f(1.44269504f * (s - m_new));
-    l_run = l_run * alpha + p;
-    const unsigned short* vr = vb + (long)t * row_stride + dchunk;
-    ushort8 vv8 = *(const ushort8*)vr;
-    #pragma unroll
-    for (int j = 0; j < 8; ++j)
-      acc[j] = fmaf(acc[j], alpha, p * bf16_to_f32(vv8[j]));
-    m_run = m_new;
-  }
-
-  // block-combine the 16 (wave, row-slot) partials, wave 0 writes scratch
-  __shared__ float sm[16], sl[16], so[16][128];
-  const int slot = wave * 4 + tsub;
-  if ((lane & 15) == 0) {
-    sm[slot] = m_run;
-    sl[slot] = l_run;
-  }
-  #pragma unroll
-  for (int j = 0; j < 8; ++j) so[slot][dchunk + j] = acc[j];
-  __syncthreads();
-  if (wave == 0) {
-    float m_t = -3.0e38f;
-    #pragma unroll
-    for (int i = 0; i < 16; ++i) m_t = fmaxf(m_t, sm[i]);
-    float l_t = 0.f;
-    float out[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    #pragma unroll
-    for (int i = 0; i < 16; ++i) {
-      const float w = __builtin_amdgcn_exp2f(1.44269504f * (sm[i] - m_t));
-      l_t += sl[i] * w;
-      #pragma unroll
-      for (int j = 0; j < 8; ++j)
-        out[j] = fmaf(so[i][dchunk + j], w, out[j]);
-    }
-    const long pbase = ((long)bq * split + blockIdx.y);
-    if (lane == 0) {
-      ml[pbase * 2] = m_t;       // m = -inf, l = 0 for an empty slice
-      ml[pbase * 2 + 1] = l_t;
-    }
-    if (tsub == 0) {
-      #pragma unroll
-      for (int j = 0; j < 8; ++j) oacc[pbase * HD + dchunk + j] = out[j];
-    }
-  }
+  const long pbase = (long)bq * split + blockIdx.y;
+  decode_attn_block(q + (long)bq * HD,
+                    dense_rows(kc, vc, b, hq / (Hq / Hkv), Hkv, T), t0, t1,
+                    scale, StorePartial{ml + pbase * 2, oacc + pbase * HD});
 }
 
 // pass 2: one 128-thread block per (b, hq); thread d combines SPLIT
@@ -307,6 +143,14 @@ decode_attn_merge_kernel(const float* __restrict__ ml,
   o[(long)bq * HD + d] = f32_to_bf16(out * inv);
 }
 
+extern "C" void decode_attn_merge_launch(const void* ml, const void* oacc,
+                                         void* o, int BHq, int split,
+                                         hipStream_t stream) {
+  hipLaunchKernelGGL(decode_attn_merge_kernel, dim3(BHq), dim3(128), 0,
+                     stream, (const float*)ml, (const float*)oacc,
+                     (unsigned short*)o, split);
+}
+
 extern "C" void decode_attn_split_launch(const void* q, const void* kc,
                                          const void* vc, void* ml,
                                          void* oacc, void* o,
@@ -319,7 +163,5 @@ extern "C" void decode_attn_split_launch(const void* q, const void* kc,
                      (const unsigned short*)kc, (const unsigned short*)vc,
                      (float*)ml, (float*)oacc, (const int*)len_dev, B, Hq,
                      Hkv, T, L, per_row, scale);
-  hipLaunchKernelGGL(decode_attn_merge_kernel, dim3(B * Hq), dim3(128), 0,
-                     stream, (const float*)ml, (const float*)oacc,
-                     (unsigned short*)o, split);
+  decode_attn_merge_launch(ml, oacc, o, B * Hq, split, stream);
 }
