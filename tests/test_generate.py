@@ -390,3 +390,179 @@ def test_continuous_batcher_auto_retire():
     assert 0 in cb.free_rows()
     cb.admit(0, torch.randint(0, cfg.vocab_size, (5,)))
     assert cb.active[0]
+
+
+# ---------------------------------------------------------------------------
+# Op-call traces of the serving passes. The expected sequences were recorded
+# with this recorder on the per-family passes that preceded the shared ones;
+# a change that adds, drops or reorders a dispatch fails here.
+# ---------------------------------------------------------------------------
+
+_SERVING_OPS = (
+    "rmsnorm", "rope", "flash_attention", "swiglu_packed",
+    "paged_prefill_attention", "paged_prefill_rope_cache",
+    "paged_prefill_attention_ragged", "rmsnorm_res", "decode_linear",
+    "decode_linear_swiglu", "decode_rope_cache", "decode_attention",
+    "decode_attention_dev", "paged_decode_rope_cache",
+    "paged_decode_attention",
+)
+
+
+def _record_calls(monkeypatch, targets):
+    """Wrap ``(owner, name)`` attributes so that every call made from
+    outside another wrapped call appends ``name`` to the returned list
+    (the CPU fallbacks of some ops call ``ops.rope`` themselves; those
+    inner calls are no dispatch of the pass)."""
+    calls, depth = [], [0]
+
+    def wrap(name, fn):
+        def inner(*args, **kwargs):
+            if depth[0] == 0:
+                calls.append(name)
+            depth[0] += 1
+            try:
+                return fn(*args, **kwargs)
+            finally:
+                depth[0] -= 1
+        return inner
+
+    for owner, name in targets:
+        monkeypatch.setattr(owner, name, wrap(name, getattr(owner, name)))
+    return calls
+
+
+def _trace_passes(model, calls, prefill, prefill_extend, prefill_ragged,
+                  decode_step):
+    """Run each serving pass once on B = 2 and return its op-call list by
+    name: the three prefill kinds, then one decode step per cache kind."""
+    from torchx_amd.models.generate import PagedKVCache
+
+    cfg = model.cfg
+    cpu = torch.device("cpu")
+    B, S, P = 2, 20, 16
+    tokens = torch.randint(0, cfg.vocab_size, (B, S))
+    table = torch.tensor([[1, 2], [3, 4]], dtype=torch.int32)
+    pos = torch.full((B,), S, dtype=torch.int32)
+
+    def dense():
+        return [KVCache.empty(cfg, B, 2 * P, cpu)
+                for _ in range(cfg.num_layers)]
+
+    def paged():
+        return [PagedKVCache.empty(cfg, 5, P, table, cpu)
+                for _ in range(cfg.num_layers)]
+
+    def run(fn, *args, **kwargs):
+        calls.clear()
+        fn(model, *args, **kwargs)
+        return list(calls)
+
+    out = {}
+    d, pg = dense(), paged()
+    out["prefill"] = run(prefill, tokens, d)
+    out["prefill_paged"] = run(prefill, tokens, pg)
+    out["prefill_extend"] = run(prefill_extend, tokens[:, :7], paged(), 0)
+    out["prefill_ragged"] = run(prefill_ragged, tokens.reshape(-1), paged(),
+                                [0, 1], [S, S], [0, 0])
+    nxt = tokens[:, -1:]
+    out["decode_paged"] = run(decode_step, nxt, pg, pos_dev=pos)
+    out["decode_rows"] = run(decode_step, nxt, dense(), pos_dev=pos)
+    out["decode_dense"] = run(decode_step, nxt, d)
+    return out
+
+
+def _decode_trace(rope_cache, attention, mlp, layers):
+    layer = (["decode_linear", rope_cache, attention, "decode_linear",
+              "rmsnorm_res"] + mlp + ["rmsnorm_res"])
+    return ["rmsnorm_res"] + layers * layer + ["decode_linear"]
+
+
+def test_serving_passes_op_call_trace(monkeypatch):
+    from torchx_amd import ops
+    from torchx_amd.models.generate import prefill_extend, prefill_ragged
+
+    torch.manual_seed(20)
+    cfg = llama_tiny()
+    assert cfg.num_layers == 2
+    model = LlamaModel(cfg)
+    calls = _record_calls(monkeypatch, [(ops, n) for n in _SERVING_OPS])
+    got = _trace_passes(model, calls, prefill, prefill_extend, prefill_ragged,
+                        decode_step)
+
+    mlp = ["rmsnorm", "swiglu_packed"]
+    dense_prefill = 2 * (["rmsnorm", "rope", "rope", "flash_attention"]
+                         + mlp) + ["rmsnorm"]
+    assert got["prefill"] == dense_prefill
+    assert got["prefill_paged"] == dense_prefill
+    assert got["prefill_extend"] == 2 * (
+        ["rmsnorm", "rope", "rope", "paged_prefill_attention"] + mlp
+    ) + ["rmsnorm"]
+    assert got["prefill_ragged"] == 2 * (
+        ["rmsnorm", "paged_prefill_rope_cache",
+         "paged_prefill_attention_ragged"] + mlp
+    ) + ["rmsnorm"]
+
+    mlp = ["decode_linear_swiglu", "decode_linear"]
+    want = {
+        "decode_dense": _decode_trace("decode_rope_cache",
+                                      "decode_attention", mlp, 2),
+        "decode_rows": _decode_trace("decode_rope_cache",
+                                     "decode_attention_dev", mlp, 2),
+        "decode_paged": _decode_trace("paged_decode_rope_cache",
+                                      "paged_decode_attention", mlp, 2),
+    }
+    for kind, trace in want.items():
+        assert got[kind] == trace, kind
+        # 8 dispatches per layer (docs/kernels.md), the leading norm and
+        # the lm_head GEMV
+        assert len(got[kind]) == 1 + 8 * cfg.num_layers + 1, kind
+
+
+@pytest.mark.parametrize("S0", [32, 33], ids=["S0%P==0", "S0%P==1"])
+def test_paged_batcher_refused_shared_admit_leaves_nothing(S0):
+    """A prompt that shares pages and is refused for lack of pages leaves
+    the table, refcounts, index and shared_tokens as they were. At these
+    lengths the hit cap ``(S0 - 1) // P`` and the registration range
+    ``S0 // P`` differ (or just stop differing)."""
+    from torchx_amd.models.generate import OutOfPages, PagedBatcher
+
+    torch.manual_seed(21)
+    cfg = llama_tiny()
+    model = LlamaModel(cfg)
+    P = 16
+    head = torch.randint(0, cfg.vocab_size, (33,))
+    p0 = torch.cat([head, torch.randint(0, cfg.vocab_size, (5,))])   # 38
+    p1 = head[:S0]
+    hits = (S0 - 1) // P                  # 1 page at 32, 2 pages at 33
+    fresh = -(-(S0 + 1) // P) - hits      # 2 pages at 32, 1 page at 33
+    usable = 3 + fresh
+    pb = PagedBatcher(model, max_batch=2, max_len=96, num_pages=1 + usable,
+                      page_size=P, prefix_sharing=True)
+    al = pb.allocator
+    pb.admit(0, p0)                       # 3 pages, 2 of them indexed
+    assert len(pb._index) == 2 and pb.free_pages() == fresh
+    other = al.alloc(1)                   # someone else's page
+    table = pb.block_table.clone()
+    refs = [al.refcount(p) for p in range(al.num_pages)]
+    index, page_key = dict(pb._index), dict(pb._page_key)
+    with pytest.raises(OutOfPages):
+        pb.admit(1, p1)                   # one page short
+    assert torch.equal(pb.block_table, table)
+    assert [al.refcount(p) for p in range(al.num_pages)] == refs
+    assert pb._index == index and pb._page_key == page_key
+    assert pb.shared_tokens == [0, 0] and pb.pages[1] == []
+    assert pb.free_rows() == [1] and pb.free_pages() == fresh - 1
+
+    al.free(other)
+    first = int(pb.admit(1, p1))
+    assert first == int(generate(model, p1.reshape(1, -1), 1)[0, S0])
+    assert pb.shared_tokens == [0, hits * P]
+    assert pb.pages[1][:hits] == pb.pages[0][:hits]
+    assert pb.free_pages() == 0
+    # its own second page at S0 = 32 duplicates an indexed key: not indexed
+    assert pb._index == index and pb._page_key == page_key
+    pb.retire(0)
+    pb.retire(1)
+    assert pb._index == {} and pb._page_key == {}
+    assert pb.free_pages() == usable
+    assert all(al.refcount(p) == 0 for p in range(al.num_pages))

@@ -13,7 +13,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 
 
-def run_batcher(args, model, tokens, fns):
+def run_batcher(args, model, tokens):
     """Admit the rows one at a time through PagedBatcher (time to first
     token per admit, by device events), then time the ragged decode."""
     from torchx_amd.models.generate import PagedBatcher
@@ -29,7 +29,7 @@ def run_batcher(args, model, tokens, fns):
     def batcher():
         return PagedBatcher(model, B, max_len, B * -(-max_len // P) + 1, P,
                             prefix_sharing=shared is not None,
-                            prefill_chunk=args.prefill_chunk, **fns)
+                            prefill_chunk=args.prefill_chunk)
 
     # warm every prefill shape (hipBLASLt algo selection) on a batcher
     # that is thrown away, then time on a fresh one
@@ -80,14 +80,14 @@ def _spread(ts):
     return ts[len(ts) // 2], ts[0], ts[-1]
 
 
-def run_admit_many(args, model, tokens, fns, dense_prefill, rounds=5):
+def run_admit_many(args, model, tokens, rounds=5):
     """Time to first token of all rows: one ``admit_many`` call against
     the one-at-a-time ``admit`` loop and, for scale, the dense [B, S]
     ``prefill``. Each is warmed on throw-away state, then the three
     alternate within every round on fresh batchers; device-event times,
     median and [min..max] over the rounds. Then the ragged decode of the
     last ``admit_many`` batcher is timed as ``run_batcher`` does."""
-    from torchx_amd.models.generate import KVCache, PagedBatcher
+    from torchx_amd.models.generate import KVCache, PagedBatcher, prefill
 
     B, S0 = tokens.shape
     N, P = args.new, args.page_size
@@ -102,7 +102,7 @@ def run_admit_many(args, model, tokens, fns, dense_prefill, rounds=5):
     def batcher():
         return PagedBatcher(model, B, max_len, B * -(-max_len // P) + 1, P,
                             prefix_sharing=shared is not None,
-                            prefill_chunk=args.prefill_chunk, **fns)
+                            prefill_chunk=args.prefill_chunk)
 
     def timed(fn):
         start = torch.cuda.Event(enable_timing=True)
@@ -125,7 +125,7 @@ def run_admit_many(args, model, tokens, fns, dense_prefill, rounds=5):
     def dense():
         caches = [KVCache.empty(model.cfg, B, max_len, tokens.device)
                   for _ in range(model.cfg.num_layers)]
-        return lambda: dense_prefill(model, tokens, caches)
+        return lambda: prefill(model, tokens, caches)
 
     for make in (many, loop):                    # warm both (GEMM shapes)
         make(batcher())()
@@ -222,16 +222,14 @@ def main():
               "need --paged", file=sys.stderr)
         return 1
 
-    from torchx_amd.models.generate import KVCache, PagedKVCache, prefill
-    from torchx_amd.models.generate import decode_step as decode_step_dense
+    from torchx_amd.models.generate import (
+        KVCache, PagedKVCache, decode_step, prefill,
+    )
     from torchx_amd.models.llama import LlamaModel, llama3_8b, llama_gpu_tiny
 
     dev = torch.device("cuda:0")
     moe = args.model.startswith("mixtral")
     if moe:
-        from torchx_amd.models.generate_moe import (
-            decode_step_moe, prefill_moe,
-        )
         from torchx_amd.models.mixtral import (
             MixtralModel, mixtral_8x7b, mixtral_gpu_tiny,
         )
@@ -244,27 +242,16 @@ def main():
                else mixtral_gpu_tiny())
         torch.manual_seed(0)
         model = MixtralModel(cfg, device=dev)
-        prefill, decode_step = prefill_moe, decode_step_moe
     else:
         cfg = llama3_8b() if args.model == "llama3_8b" else llama_gpu_tiny()
         torch.manual_seed(0)
         model = LlamaModel(cfg, device=dev)
-        decode_step = decode_step_dense
     B, S0, N = args.batch, args.prompt, args.new
     tokens = torch.randint(0, cfg.vocab_size, (B, S0), device=dev)
     if args.batcher:
-        if moe:
-            from torchx_amd.models.generate_moe import (
-                prefill_extend_moe, prefill_ragged_moe,
-            )
-            fns = dict(prefill_fn=prefill, decode_fn=decode_step,
-                       extend_fn=prefill_extend_moe,
-                       ragged_fn=prefill_ragged_moe)
-        else:
-            fns = {}
         if args.admit_many:
-            return run_admit_many(args, model, tokens, fns, prefill)
-        return run_batcher(args, model, tokens, fns)
+            return run_admit_many(args, model, tokens)
+        return run_batcher(args, model, tokens)
     if args.paged:
         # every sequence gets M pages; the table is a seeded permutation
         # of the physical pages so they are not accidentally contiguous

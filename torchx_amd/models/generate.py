@@ -1,5 +1,6 @@
-"""Serving-side generation for the Llama family: prefill + KV-cache
-decode on the CDNA4 kernels.
+"""Serving-side generation for the Llama and Mixtral families: prefill +
+KV-cache decode on the CDNA4 kernels. One body per kind of pass serves
+both; ``_mlp_prefill`` / ``_mlp_decode`` hold what differs.
 
 The training path never materializes K/V (the fused qkv attention keeps
 them inside the kernel), so generation runs its own per-layer loop over
@@ -186,37 +187,74 @@ def _split_qkv(qkv: torch.Tensor, cfg: LlamaConfig):
             v.reshape(B, S, cfg.num_kv_heads, cfg.head_dim).contiguous())
 
 
-@torch.no_grad()
-def prefill(model: LlamaModel, tokens: torch.Tensor,
-            caches: list) -> torch.Tensor:
-    """Run the prompt through the model, filling per-layer KV caches.
-    Returns the last position's logits [B, vocab]."""
+def _mlp_prefill(blk, xn: torch.Tensor) -> torch.Tensor:
+    """MLP half of a block in a prefill pass: normed activations in, the
+    block's MLP output out. With ``_mlp_decode`` this is all the serving
+    passes know about the model family: a MixtralBlock has ``moe``, a
+    LlamaBlock has ``wgu`` / ``wdown``."""
+    if "moe" in blk._modules:
+        return blk.moe(xn)
+    return blk.wdown(ops.swiglu_packed(blk.wgu(xn)))
+
+
+def _mlp_decode(blk, xn: torch.Tensor) -> torch.Tensor:
+    """``_mlp_prefill`` for a decode micro-batch xn [B, H] -> [B, H]. A
+    Python branch taken while the step is recorded, so a hipGraph capture
+    of the dense step holds only the two GEMVs."""
+    if "moe" in blk._modules:
+        # generate_moe imports this module
+        from .generate_moe import _moe_mlp_decode
+        return _moe_mlp_decode(blk.moe, xn)
+    return ops.decode_linear(ops.decode_linear_swiglu(xn, blk.wgu.weight),
+                             blk.wdown.weight)
+
+
+def _prefill_pass(model, tokens: torch.Tensor, caches: list, start: int,
+                  attend) -> torch.Tensor:
+    """Body of the [B, S] prefill passes, tokens at positions
+    ``start .. start+S-1``. The attention half of a block is norm, wqkv,
+    both ropes, ``attend(cache, q, k, v)`` — which puts the roped K/V
+    where the pass keeps them and runs its attention op — and wo +
+    residual. Returns the last position's logits [B, vocab]."""
     cfg = model.cfg
     B, S = tokens.shape
-    cos = model.rope_cos[:S]
-    sin = model.rope_sin[:S]
+    cos = model.rope_cos[start:start + S]
+    sin = model.rope_sin[start:start + S]
     x = model.embed(tokens)
     for blk, cache in zip(model.blocks, caches):
         xn = ops.rmsnorm(x, blk.attn_norm, cfg.rms_eps)
         q, k, v = _split_qkv(blk.wqkv(xn), cfg)
         q = ops.rope(q, cos, sin)
         k = ops.rope(k, cos, sin)
+        attn = attend(cache, q, k, v)
+        x = x + blk.wo(attn.reshape(B, S, cfg.q_dim))
+        xn = ops.rmsnorm(x, blk.mlp_norm, cfg.rms_eps)
+        x = x + _mlp_prefill(blk, xn)
+    x = ops.rmsnorm(x, model.final_norm, cfg.rms_eps)
+    return model.lm_head(x[:, -1])
+
+
+@torch.no_grad()
+def prefill(model, tokens: torch.Tensor, caches: list) -> torch.Tensor:
+    """Run the prompt through the model (Llama or Mixtral), filling
+    per-layer KV caches of either kind; attention is the dense training
+    kernel. Returns the last position's logits [B, vocab]."""
+    S = tokens.shape[1]
+
+    def attend(cache, q, k, v):
         if isinstance(cache, PagedKVCache):
             cache.store_prefix(k, v)
         else:
             cache.k[:, :S] = k
             cache.v[:, :S] = v
             cache.length = S
-        attn = ops.flash_attention(q, k, v, causal=True)
-        x = x + blk.wo(attn.reshape(B, S, cfg.q_dim))
-        xn = ops.rmsnorm(x, blk.mlp_norm, cfg.rms_eps)
-        x = x + blk.wdown(ops.swiglu_packed(blk.wgu(xn)))
-    x = ops.rmsnorm(x, model.final_norm, cfg.rms_eps)
-    return model.lm_head(x[:, -1])
+        return ops.flash_attention(q, k, v, causal=True)
+
+    return _prefill_pass(model, tokens, caches, 0, attend)
 
 
 @torch.no_grad()
-def prefill_extend(model: LlamaModel, tokens: torch.Tensor, caches: list,
+def prefill_extend(model, tokens: torch.Tensor, caches: list,
                    ctx: int) -> torch.Tensor:
     """Prefill a piece of a prompt behind ``ctx`` rows the paged caches
     already hold: tokens [B, S] sit at positions ctx .. ctx+S-1. Their
@@ -224,30 +262,20 @@ def prefill_extend(model: LlamaModel, tokens: torch.Tensor, caches: list,
     the block table (``ops.paged_prefill_attention``), so the cached rows
     are neither recomputed nor copied. Returns the last position's logits
     [B, vocab]. ``ctx = 0`` with the whole prompt is a paged ``prefill``."""
-    cfg = model.cfg
     B, S = tokens.shape
     assert ctx >= 0 and S >= 1
     assert ctx + S <= model.rope_cos.shape[0], "beyond the rope tables"
-    cos = model.rope_cos[ctx:ctx + S]
-    sin = model.rope_sin[ctx:ctx + S]
     ctx_dev = torch.full((B,), ctx, dtype=torch.int32, device=tokens.device)
-    x = model.embed(tokens)
-    for blk, cache in zip(model.blocks, caches):
+
+    def attend(cache, q, k, v):
         assert isinstance(cache, PagedKVCache), "paged caches only"
         assert ctx + S <= cache.block_table.shape[1] * cache.page_size, \
             "beyond the block table"
-        xn = ops.rmsnorm(x, blk.attn_norm, cfg.rms_eps)
-        q, k, v = _split_qkv(blk.wqkv(xn), cfg)
-        q = ops.rope(q, cos, sin)
-        k = ops.rope(k, cos, sin)
         cache.store_rows(k, v, ctx)
-        attn = ops.paged_prefill_attention(q, cache.kpool, cache.vpool,
+        return ops.paged_prefill_attention(q, cache.kpool, cache.vpool,
                                            cache.table_rows(B), ctx_dev)
-        x = x + blk.wo(attn.reshape(B, S, cfg.q_dim))
-        xn = ops.rmsnorm(x, blk.mlp_norm, cfg.rms_eps)
-        x = x + blk.wdown(ops.swiglu_packed(blk.wgu(xn)))
-    x = ops.rmsnorm(x, model.final_norm, cfg.rms_eps)
-    return model.lm_head(x[:, -1])
+
+    return _prefill_pass(model, tokens, caches, ctx, attend)
 
 
 @dataclass
@@ -317,7 +345,7 @@ def _ragged_logits(model, x: torch.Tensor, rp: RaggedPass) -> torch.Tensor:
 
 
 @torch.no_grad()
-def prefill_ragged(model: LlamaModel, tokens: torch.Tensor, caches: list,
+def prefill_ragged(model, tokens: torch.Tensor, caches: list,
                    rows, q_lens, ctx) -> torch.Tensor:
     """``prefill_extend`` for several sequences of different lengths in
     ONE pass. tokens [T] holds the chunks packed back to back: sequence b
@@ -336,12 +364,12 @@ def prefill_ragged(model: LlamaModel, tokens: torch.Tensor, caches: list,
     for blk, cache in zip(model.blocks, caches):
         x = _ragged_attention(model, blk, cache, x, rp)
         xn = ops.rmsnorm(x, blk.mlp_norm, cfg.rms_eps)
-        x = x + blk.wdown(ops.swiglu_packed(blk.wgu(xn)))
+        x = x + _mlp_prefill(blk, xn)
     return _ragged_logits(model, x, rp)
 
 
 @torch.no_grad()
-def decode_step(model: LlamaModel, token: torch.Tensor, caches: list,
+def decode_step(model, token: torch.Tensor, caches: list,
                 pos_dev: Optional[torch.Tensor] = None) -> torch.Tensor:
     """One token [B, 1] -> next-position logits [B, vocab], appending to
     the caches. Fully fused decode layer (8 dispatches on GPU): skinny-M
@@ -352,7 +380,10 @@ def decode_step(model: LlamaModel, token: torch.Tensor, caches: list,
     the step RAGGED — every sequence at its own cache position
     (continuous batching, see ContinuousBatcher). ``PagedKVCache``
     caches take the same [B] vector and go through the block-table
-    kernels (see PagedBatcher)."""
+    kernels (see PagedBatcher). A Mixtral model runs the same step with
+    its active-expert MLP half (``_mlp_decode``), which is
+    position-independent; its routing reads the device, so only the
+    dense model's step is capturable."""
     cfg = model.cfg
     B = token.shape[0]
     blocks = model.blocks
@@ -385,8 +416,7 @@ def decode_step(model: LlamaModel, token: torch.Tensor, caches: list,
                 o = ops.decode_attention_dev(q, cache.k, cache.v, pos_dev)
         a = ops.decode_linear(o.reshape(B, -1), blk.wo.weight)
         x, xn = ops.rmsnorm_res(x, a, blk.mlp_norm, cfg.rms_eps)
-        m = ops.decode_linear(ops.decode_linear_swiglu(xn, blk.wgu.weight),
-                              blk.wdown.weight)
+        m = _mlp_decode(blk, xn)
         w_next = (blocks[i + 1].attn_norm if i + 1 < len(blocks)
                   else model.final_norm)
         x, xn = ops.rmsnorm_res(x, m, w_next, cfg.rms_eps)
@@ -395,15 +425,15 @@ def decode_step(model: LlamaModel, token: torch.Tensor, caches: list,
 
 @torch.no_grad()
 def generate(
-    model: LlamaModel,
+    model,
     tokens: torch.Tensor,
     max_new_tokens: int,
     temperature: float = 0.0,
     top_k: Optional[int] = None,
     max_len: Optional[int] = None,
 ) -> torch.Tensor:
-    """Greedy (temperature=0) or top-k sampled continuation.
-    tokens [B, S0] -> [B, S0 + max_new_tokens]."""
+    """Greedy (temperature=0) or top-k sampled continuation, for a Llama
+    or a Mixtral model. tokens [B, S0] -> [B, S0 + max_new_tokens]."""
     cfg = model.cfg
     B, S0 = tokens.shape
     total = S0 + max_new_tokens
@@ -509,23 +539,13 @@ def generate_graphed(model: LlamaModel, tokens: torch.Tensor,
     return torch.cat(out, dim=1)
 
 
-class ContinuousBatcher:
-    """Continuous batching over a fixed pool of cache rows: sequences of
-    DIFFERENT lengths decode together in one ragged step (int32 [B]
-    position vector drives rope, cache append and attention per row), and
-    a finished row can be re-admitted with a new prompt while the others
-    keep decoding — the serving pattern behind vLLM-style engines,
-    without paging (288 GB HBM3E holds the whole [B, T] cache pool).
+class _Batcher:
+    """What the two batchers share: the model, the passes they run and the
+    per-row decode state. ``prefill_fn`` / ``decode_fn`` are hooks that
+    replace a pass; the defaults serve Llama and Mixtral alike."""
 
-    Greedy decoding; rows are independent — admit() prefills ONE row's
-    cache slice, step() advances every active row one token.
-    """
-
-    def __init__(self, model, max_batch: int, max_len: int,
-                 prefill_fn=None, decode_fn=None):
-        """``prefill_fn``/``decode_fn`` default to the dense Llama path;
-        pass ``generate_moe.prefill_moe`` / ``decode_step_moe`` to run a
-        Mixtral pool (the MoE step takes the same ``pos_dev`` vector)."""
+    def __init__(self, model, max_batch: int, max_len: int, prefill_fn,
+                 decode_fn):
         self.model = model
         self.cfg = model.cfg
         self._prefill = prefill_fn or prefill
@@ -534,8 +554,6 @@ class ContinuousBatcher:
         dev = next(model.parameters()).device
         self.device = dev
         self.max_len = max_len
-        self.caches = [KVCache.empty(self.cfg, max_batch, max_len, dev)
-                       for _ in range(self.cfg.num_layers)]
         self.pos = torch.zeros(max_batch, dtype=torch.int32, device=dev)
         # host mirror of pos (deterministic: admit sets it, step adds 1) —
         # overflow checks never touch the device
@@ -545,6 +563,28 @@ class ContinuousBatcher:
 
     def free_rows(self) -> list:
         return [i for i, a in enumerate(self.active) if not a]
+
+
+class ContinuousBatcher(_Batcher):
+    """Continuous batching over a fixed pool of cache rows: sequences of
+    DIFFERENT lengths decode together in one ragged step (int32 [B]
+    position vector drives rope, cache append and attention per row), and
+    a finished row can be re-admitted with a new prompt while the others
+    keep decoding — the serving pattern behind vLLM-style engines,
+    without paging (288 GB HBM3E holds the whole [B, T] cache pool).
+
+    Greedy decoding; rows are independent — admit() prefills ONE row's
+    cache slice, step() advances every active row one token. The model
+    may be a Llama or a Mixtral; ``prefill_fn`` / ``decode_fn`` are hooks
+    that replace ``prefill`` / ``decode_step``.
+    """
+
+    def __init__(self, model, max_batch: int, max_len: int,
+                 prefill_fn=None, decode_fn=None):
+        super().__init__(model, max_batch, max_len, prefill_fn, decode_fn)
+        self.caches = [KVCache.empty(self.cfg, max_batch, max_len,
+                                     self.device)
+                       for _ in range(self.cfg.num_layers)]
 
     @torch.no_grad()
     def admit(self, row: int, prompt: torch.Tensor) -> torch.Tensor:
@@ -591,7 +631,7 @@ class ContinuousBatcher:
         return nxt.reshape(-1)
 
 
-class PagedBatcher:
+class PagedBatcher(_Batcher):
     """Continuous batching over a PAGED KV pool: same surface as
     ContinuousBatcher (``free_rows``, ``admit``, ``retire``, ``step``),
     but cache memory is committed per ``page_size`` tokens actually
@@ -608,9 +648,8 @@ class PagedBatcher:
     appended to ``self.preempted``.
 
     ``prefill_chunk=N`` prefills a prompt in pieces of at most N tokens
-    through ``extend_fn`` (default ``prefill_extend``; pass
-    ``generate_moe.prefill_extend_moe`` for Mixtral), which bounds the
-    transient activation memory of a long prompt.
+    through ``prefill_extend``, which bounds the transient activation
+    memory of a long prompt.
 
     ``prefix_sharing=True`` lets a new request map the pages of a live
     row whose prompt starts with the same tokens instead of recomputing
@@ -626,13 +665,18 @@ class PagedBatcher:
     — so there is no copy-on-write. A page leaves the index when its last
     holder frees it; a holder of a child page always holds the parent, so
     no stale chain survives a page's reuse. With both options off,
-    ``admit`` is the whole-prompt dense-kernel path.
+    ``admit`` is the whole-prompt dense-kernel path (``prefill`` on the
+    row's caches).
 
     ``admit_many`` admits several requests in one call and prefills them
-    together, packed, through ``ragged_fn`` (default ``prefill_ragged``;
-    pass ``generate_moe.prefill_ragged_moe`` for Mixtral); it honours
-    both options above and leaves the same state as one ``admit`` per
-    request.
+    together, packed, through ``prefill_ragged``; it honours both options
+    above and leaves the same state as one ``admit`` per request.
+
+    The model may be a Llama or a Mixtral: the passes tell them apart by
+    the block. ``prefill_fn``, ``decode_fn``, ``extend_fn`` and
+    ``ragged_fn`` are hooks that replace ``prefill``, ``decode_step``,
+    ``prefill_extend`` and ``prefill_ragged`` (to count calls, say); no
+    model needs them.
     """
 
     def __init__(self, model, max_batch: int, max_len: int, num_pages: int,
@@ -640,10 +684,7 @@ class PagedBatcher:
                  prefix_sharing: bool = False,
                  prefill_chunk: Optional[int] = None, extend_fn=None,
                  ragged_fn=None):
-        self.model = model
-        self.cfg = model.cfg
-        self._prefill = prefill_fn or prefill
-        self._decode = decode_fn or decode_step
+        super().__init__(model, max_batch, max_len, prefill_fn, decode_fn)
         self._extend = extend_fn or prefill_extend
         self._ragged = ragged_fn or prefill_ragged
         assert prefill_chunk is None or prefill_chunk >= 1
@@ -653,10 +694,7 @@ class PagedBatcher:
         self._index = {}
         self._page_key = {}
         self.shared_tokens = [0] * max_batch
-        assert max_len <= self.cfg.max_seq_len, "beyond the rope tables"
-        dev = next(model.parameters()).device
-        self.device = dev
-        self.max_len = max_len
+        dev = self.device
         self.page_size = page_size
         self.table_width = -(-max_len // page_size)
         self.block_table = torch.zeros(max_batch, self.table_width,
@@ -666,16 +704,9 @@ class PagedBatcher:
                        for _ in range(self.cfg.num_layers)]
         self.allocator = PageAllocator(num_pages)
         self.pages = [[] for _ in range(max_batch)]  # pages owned per row
-        self.pos = torch.zeros(max_batch, dtype=torch.int32, device=dev)
-        self.pos_host = [0] * max_batch
         # 1 for active rows: only those advance (pos.add_(mask))
         self.mask = torch.zeros(max_batch, dtype=torch.int32, device=dev)
-        self.tok = torch.zeros(max_batch, 1, dtype=torch.long, device=dev)
-        self.active = [False] * max_batch
         self.preempted = []
-
-    def free_rows(self) -> list:
-        return [i for i, a in enumerate(self.active) if not a]
 
     def free_pages(self) -> int:
         return self.allocator.num_free
@@ -689,47 +720,32 @@ class PagedBatcher:
         assert not self.active[row], f"row {row} is occupied"
         S0 = prompt.numel()
         assert S0 + 1 < self.max_len
-        P = self.page_size
         if self.prefix_sharing or self.prefill_chunk is not None:
             return self._admit_extend(row, prompt)
-        pages = self.allocator.alloc(-(-(S0 + 1) // P))
-        self.pages[row] = pages
-        self.block_table[row, :len(pages)] = torch.tensor(
-            pages, dtype=torch.int32, device=self.device)
+        self._set_pages(
+            row, self.allocator.alloc(-(-(S0 + 1) // self.page_size)))
         logits = self._prefill(self.model,
                                prompt.reshape(1, S0).to(self.device),
                                [c.for_row(row) for c in self.caches])
         nxt = logits.argmax(-1)
-        self.tok[row, 0] = nxt[0]
-        self.pos[row] = S0
-        self.mask[row] = 1
-        self.pos_host[row] = S0
-        self.active[row] = True
+        self._activate([row], nxt, [S0])
         return nxt[0]
 
     def _admit_extend(self, row: int, prompt: torch.Tensor) -> torch.Tensor:
         """``admit`` through ``extend_fn``: map the cached head of the
         prompt (prefix sharing), prefill the rest in pieces."""
         S0 = prompt.numel()
-        P = self.page_size
-        toks = prompt.reshape(-1).tolist()
-        hits = []
-        if self.prefix_sharing:
-            parent = -1
-            for j in range((S0 - 1) // P):
-                page = self._index.get((parent, tuple(toks[j * P:(j + 1) * P])))
-                if page is None:
-                    break
-                hits.append(page)
-                parent = page
-        # all-or-nothing, and before anything else changes
-        fresh = self.allocator.alloc(-(-(S0 + 1) // P) - len(hits))
+        # all-or-nothing: _place_prompt allocates before it registers
+        # anything, and alloc raises without changing state. The prompt's
+        # pages join the index before they are filled; nothing reads the
+        # index until the prefill below is done, and this call has no later
+        # prompt that could map them.
+        hits, pages = self._place_prompt(
+            prompt.reshape(-1).tolist(), self._index, self._page_key,
+            self.allocator.alloc)
         self.allocator.share(hits)
-        pages = hits + fresh
-        self.pages[row] = pages
-        self.block_table[row, :len(pages)] = torch.tensor(
-            pages, dtype=torch.int32, device=self.device)
-        ctx = len(hits) * P
+        self._set_pages(row, pages)
+        ctx = len(hits) * self.page_size
         self.shared_tokens[row] = ctx
         piece = self.prefill_chunk or (S0 - ctx)
         row_caches = [c.for_row(row) for c in self.caches]
@@ -739,25 +755,24 @@ class PagedBatcher:
             logits = self._extend(self.model, prompt_dev[:, ctx:ctx + n],
                                   row_caches, ctx)
             ctx += n
-        if self.prefix_sharing:
-            # register this row's full prompt pages; stop at a page whose
-            # key another row's page already holds (the cap above can
-            # leave one), so every indexed child's parent is a page this
-            # row holds
-            parent = -1
-            for j in range(S0 // P):
-                key = (parent, tuple(toks[j * P:(j + 1) * P]))
-                if self._index.setdefault(key, pages[j]) != pages[j]:
-                    break
-                self._page_key[pages[j]] = key
-                parent = pages[j]
         nxt = logits.argmax(-1)
-        self.tok[row, 0] = nxt[0]
-        self.pos[row] = S0
-        self.mask[row] = 1
-        self.pos_host[row] = S0
-        self.active[row] = True
+        self._activate([row], nxt, [S0])
         return nxt[0]
+
+    def _set_pages(self, row: int, pages: list) -> None:
+        self.pages[row] = pages
+        self.block_table[row, :len(pages)] = torch.tensor(
+            pages, dtype=torch.int32, device=self.device)
+
+    def _activate(self, rows, first: torch.Tensor, lens) -> None:
+        """Make ``rows`` live: row ``rows[i]`` holds a prompt of
+        ``lens[i]`` tokens and decodes on from ``first[i]``."""
+        for i, (row, S0) in enumerate(zip(rows, lens)):
+            self.tok[row, 0] = first[i]
+            self.pos[row] = S0
+            self.mask[row] = 1
+            self.pos_host[row] = S0
+            self.active[row] = True
 
     def _count_fresh_pages(self, prompts_toks: list) -> int:
         """Dry run of ``admit_many``'s allocation: the pages the prompts
@@ -881,14 +896,7 @@ class PagedBatcher:
                 k_dev = torch.tensor([k for k, _ in done], device=self.device)
                 i_dev = torch.tensor([i for _, i in done], device=self.device)
                 first[i_dev] = logits[k_dev].argmax(-1)
-        lens = [len(t) for t in toks]
-        self.tok[rows_dev, 0] = first
-        self.pos[rows_dev] = torch.tensor(lens, dtype=torch.int32,
-                                          device=self.device)
-        self.mask[rows_dev] = 1
-        for row, S0 in zip(rows, lens):
-            self.pos_host[row] = S0
-            self.active[row] = True
+        self._activate(rows, first, [len(t) for t in toks])
         return first
 
     def retire(self, row: int) -> None:
