@@ -209,7 +209,16 @@ def main():
                         "admit_many call (packed ragged prefill) and report "
                         "its time next to the one-at-a-time loop and the "
                         "dense prefill, alternated in this process")
+    p.add_argument("--moe-decode", choices=["fused", "loop"], default=None,
+                   help="Mixtral decode MLP: the device-routed grouped "
+                        "expert GEMV kernels (fused) or the per-expert loop "
+                        "with one host sync per layer (loop); default: "
+                        "TORCHX_AMD_MOE_DECODE, else fused")
     args = p.parse_args()
+    if args.moe_decode is not None:
+        from torchx_amd import ops
+
+        ops.set_moe_decode_impl(args.moe_decode)
     if args.admit_many:
         args.batcher = True
     if args.paged and args.graph:
@@ -222,6 +231,7 @@ def main():
               "need --paged", file=sys.stderr)
         return 1
 
+    from torchx_amd import ops
     from torchx_amd.models.generate import (
         KVCache, PagedKVCache, decode_step, prefill,
     )
@@ -319,6 +329,7 @@ def main():
         "model": args.model, "dtype": "bf16", "data": "synthetic", "graphed": bool(args.graph),
         "kv_cache": "paged" if args.paged else "dense",
         "page_size": args.page_size if args.paged else None,
+        "moe_decode": ops.get_moe_decode_impl() if moe else None,
     }))
     return 0
 

@@ -10,7 +10,12 @@ Mixtral model. What is Mixtral's own is the decode MLP half below: top-k
 expert routing where, at decode batch B, every (token, expert) group
 runs the fused GEMV+SwiGLU expert FFN on its tokens only, so each step
 streams just the ACTIVE experts' weights (<= B*top_k of num_experts per
-layer). In prefill the MLP half is the training ``MoELayer`` itself.
+layer). Router, top-k and softmax run on the device and
+``ops.moe_decode_mlp`` reads their result there: its two grouped expert
+GEMV kernels (ops/csrc/moe_gemv.hip) are the whole MLP half, with no
+host sync (``ops.set_moe_decode_impl("loop")`` brings back the
+per-expert loop with its one sync per layer; same bits). In prefill the
+MLP half is the training ``MoELayer`` itself.
 
 Single-rank serving only (``ep_size == 1`` — all experts local); the
 expert-parallel all-to-all path in models/mixtral.py is a training
@@ -34,27 +39,28 @@ __all__ = ["prefill_moe", "prefill_extend_moe", "prefill_ragged_moe",
            "decode_step_moe", "generate_moe", "KVCache"]
 
 
+def _expert_weights(moe: MoELayer):
+    """The experts' (wgu, wdown) weight lists, built once per layer. They
+    hold the parameters themselves (no copy, no stacking), which ``.to()``
+    and ``load_state_dict`` update in place."""
+    cached = moe.__dict__.get("_decode_weights")
+    if cached is None:
+        cached = ([e.wgu.weight for e in moe.local_experts],
+                  [e.wdown.weight for e in moe.local_experts])
+        moe.__dict__["_decode_weights"] = cached
+    return cached
+
+
 def _moe_mlp_decode(moe: MoELayer, x: torch.Tensor) -> torch.Tensor:
-    """Top-k MoE for a decode micro-batch x [B, H] -> [B, H]; experts run
-    the skinny-M GEMV + fused SwiGLU path on their assigned tokens."""
+    """Top-k MoE for a decode micro-batch x [B, H] -> [B, H]: the routing
+    stays on the device and ``ops.moe_decode_mlp`` runs the chosen experts'
+    FFNs on their tokens."""
     assert moe.ep_size == 1, "serving path is single-rank (all experts local)"
     cfg = moe.cfg
     logits = (x @ moe.router.weight.t()).float()          # [B, E]
     w, idx = torch.topk(logits, cfg.top_k, dim=-1)
     w = torch.softmax(w, dim=-1).to(x.dtype)              # [B, k]
-    idx_h = idx.cpu()  # ONE host sync per layer; partitioning is host-side
-    out = torch.zeros_like(x)
-    for e in range(cfg.num_experts):
-        rows_h = (idx_h == e).any(-1).nonzero(as_tuple=True)[0]
-        if rows_h.numel() == 0:
-            continue
-        rows = rows_h.to(x.device, non_blocking=True)
-        exp = moe.local_experts[e]
-        h = ops.decode_linear_swiglu(x[rows], exp.wgu.weight)
-        ye = ops.decode_linear(h, exp.wdown.weight)
-        coef = (w * (idx == e)).sum(-1)[rows]             # [n], on device
-        out[rows] += ye * coef[:, None]
-    return out
+    return ops.moe_decode_mlp(x, idx, w, *_expert_weights(moe))
 
 
 # the shared passes tell a MixtralBlock from a LlamaBlock themselves

@@ -11,8 +11,9 @@ from __future__ import annotations
 
 import importlib.util
 import math
+import os
 from pathlib import Path
-from typing import Optional, Tuple
+from typing import Optional, Sequence, Tuple
 
 import torch
 
@@ -941,3 +942,98 @@ def decode_linear(x: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
     else:
         out = x2 @ w.t()
     return out.reshape(*x.shape[:-1], w.shape[0])
+
+
+# ---------------------------------------------------------------------------
+# MoE decode MLP (serving): top-k expert FFNs of a decode micro-batch —
+# ops/csrc/moe_gemv.hip. The grouped kernels read the routing from device
+# memory, so the fused path is two dispatches and never waits for the
+# device; its result is bit-identical to the per-expert loop.
+# ---------------------------------------------------------------------------
+
+_MOE_DECODE_IMPLS = ("fused", "loop")
+_moe_decode_impl = os.environ.get("TORCHX_AMD_MOE_DECODE", "fused")
+assert _moe_decode_impl in _MOE_DECODE_IMPLS, (
+    f"TORCHX_AMD_MOE_DECODE must be one of {_MOE_DECODE_IMPLS}")
+
+
+def set_moe_decode_impl(impl: str) -> None:
+    """Select the GPU path of ``moe_decode_mlp``: "fused" (default; the two
+    grouped expert GEMV kernels, routing read on the device) or "loop" (one
+    host sync, then the per-expert GEMV loop). Both produce the same bits.
+    The initial value comes from TORCHX_AMD_MOE_DECODE."""
+    global _moe_decode_impl
+    if impl not in _MOE_DECODE_IMPLS:
+        raise ValueError(f"moe decode impl must be 'fused' or 'loop', "
+                         f"got {impl!r}")
+    _moe_decode_impl = impl
+
+
+def get_moe_decode_impl() -> str:
+    return _moe_decode_impl
+
+
+def moe_decode_mlp_loop(x: torch.Tensor, idx: torch.Tensor, cw: torch.Tensor,
+                        wgu: Sequence[torch.Tensor],
+                        wdown: Sequence[torch.Tensor]) -> torch.Tensor:
+    """The per-expert loop of ``moe_decode_mlp``: one host sync for the
+    routing, then every active expert runs the skinny-M GEMV + fused SwiGLU
+    path on its tokens and is folded into ``out`` in ascending order."""
+    idx_h = idx.cpu()  # ONE host sync; partitioning is host-side
+    out = torch.zeros_like(x)
+    for e in range(len(wgu)):
+        rows_h = (idx_h == e).any(-1).nonzero(as_tuple=True)[0]
+        if rows_h.numel() == 0:
+            continue
+        rows = rows_h.to(x.device, non_blocking=True)
+        h = decode_linear_swiglu(x[rows], wgu[e])
+        ye = decode_linear(h, wdown[e])
+        coef = (cw * (idx == e)).sum(-1)[rows]            # [n], on device
+        out[rows] += ye * coef[:, None]
+    return out
+
+
+def _moe_fused_ok(x, idx, cw, wgu, wdown) -> bool:
+    if not (x.is_cuda and x.dim() == 2 and x.dtype == torch.bfloat16):
+        return False
+    B, H = x.shape
+    E = len(wgu)
+    if not (1 <= B <= 8 and 1 <= E <= 16 and len(wdown) == E):
+        return False
+    if idx.dtype != torch.int64 or idx.dim() != 2 or idx.shape[0] != B \
+            or not 1 <= idx.shape[1] <= min(8, E) \
+            or cw.shape != idx.shape or cw.dtype != torch.bfloat16:
+        return False
+    two_i = wgu[0].shape[0]
+    I = two_i // 2
+    if two_i % 2 or H % 512 or I % 512 or H == 0 or I == 0 \
+            or two_i * H >= 2 ** 31:
+        return False
+    return all(w.dtype == torch.bfloat16 and w.is_contiguous()
+               and w.device == x.device
+               for w in (*wgu, *wdown)) \
+        and all(w.shape == (two_i, H) for w in wgu) \
+        and all(w.shape == (H, I) for w in wdown)
+
+
+def moe_decode_mlp(x: torch.Tensor, idx: torch.Tensor, cw: torch.Tensor,
+                   wgu: Sequence[torch.Tensor],
+                   wdown: Sequence[torch.Tensor]) -> torch.Tensor:
+    """Top-k MoE MLP of a decode micro-batch: x [B, H] bf16, ``idx`` [B, k]
+    int64 and ``cw`` [B, k] bf16 as ``torch.topk`` / ``softmax`` return them
+    (the experts of a row distinct), ``wgu`` / ``wdown`` the E experts'
+    packed gate|up [2I, H] and down [H, I] weights (separate tensors, never
+    stacked) -> ``out[b] = sum_j cw[b, j] * down_e(swiglu(wgu_e x[b]))``,
+    e = idx[b, j], [B, H] bf16. Inference only.
+
+    On the GPU with B <= 8, k <= 8, E <= 16 and H, I multiples of 512 this
+    is two dispatches (``moe_gemv_swiglu``, ``moe_gemv_down_combine``) and
+    no host sync; everything else (CPU, larger batches, other shapes, or
+    ``set_moe_decode_impl("loop")``) runs ``moe_decode_mlp_loop``, whose
+    bits the kernels reproduce."""
+    if _moe_decode_impl == "fused" and _moe_fused_ok(x, idx, cw, wgu, wdown):
+        hip = hip_ops()
+        idx, wgu, wdown = idx.contiguous(), list(wgu), list(wdown)
+        h = hip.moe_gemv_swiglu(x.contiguous(), idx, wgu)
+        return hip.moe_gemv_down_combine(h, idx, cw.contiguous(), wdown)
+    return moe_decode_mlp_loop(x, idx, cw, wgu, wdown)

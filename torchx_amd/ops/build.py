@@ -27,10 +27,18 @@ SOURCES = [
     "decode_attn.hip",
     "paged_attn.hip",
     "gemv.hip",
+    "moe_gemv.hip",
     "fp8_cast.hip",
     "probe.hip",
     "bindings.cpp",
 ]
+
+# per-source extra flags: moe_gemv.hip keeps its fp32 arithmetic on the
+# scalar VALU forms (no packed-fp32 instructions)
+EXTRA_FLAGS = {
+    "moe_gemv.hip": ["-Xclang", "-target-feature", "-Xclang",
+                     "-packed-fp32-ops"],
+}
 
 
 def _torch_paths():
@@ -88,7 +96,8 @@ def build(force: bool = False, verbose: bool = True) -> Path:
                 and obj.stat().st_mtime > hdr_mtime \
                 and not force:
             continue
-        cmd = ["hipcc", "-c", str(src_path), "-o", str(obj)] + common_flags
+        cmd = ["hipcc", "-c", str(src_path), "-o", str(obj)] + common_flags \
+            + EXTRA_FLAGS.get(src, [])
         if src.endswith(".cpp"):
             cmd.append("-x")
             cmd.append("hip")  # bindings still need hip headers/stream types

@@ -81,6 +81,11 @@ void paged_prefill_rope_cache_launch(const void*, void*, void*, void*,
                                      const void*, const void*, const void*,
                                      const void*, long, int, int, long, int,
                                      hipStream_t);
+void moe_gemv_swiglu_launch(const void*, const void*, const void* const*,
+                            void*, int, int, int, int, int, hipStream_t);
+void moe_gemv_down_combine_launch(const void*, const void*, const void*,
+                                  const void* const*, void*, int, int, int,
+                                  int, int, hipStream_t);
 }
 
 namespace {
@@ -592,6 +597,92 @@ at::Tensor gemv_swiglu_bf16(at::Tensor x, at::Tensor w) {
   return out;
 }
 
+// ---- device-routed MoE decode MLP (moe_gemv.hip) ----------------------------
+// Routing idx [B, k] int64 and weights cw [B, k] bf16 as torch.topk /
+// softmax leave them; the experts' weights are separate tensors whose base
+// pointers go to the kernel by value.
+namespace {
+
+void check_moe_routing(const at::Tensor& idx, const at::Tensor& like, long E) {
+  TORCH_CHECK(idx.is_cuda() && idx.scalar_type() == at::kLong &&
+                  idx.dim() == 2 && idx.is_contiguous(),
+              "moe: idx must be a contiguous int64 [B, k] device tensor");
+  TORCH_CHECK(idx.device() == like.device(), "moe: idx on another device");
+  TORCH_CHECK(idx.size(0) >= 1 && idx.size(0) <= 8, "moe: B must be 1..8");
+  TORCH_CHECK(idx.size(1) >= 1 && idx.size(1) <= 8 && idx.size(1) <= E,
+              "moe: k must be 1..min(8, E)");
+}
+
+// base pointers of E same-shape [rows, cols] bf16 weights
+std::vector<const void*> moe_weight_ptrs(const std::vector<at::Tensor>& ws,
+                                         long rows, long cols,
+                                         const at::Tensor& like,
+                                         const char* name) {
+  TORCH_CHECK(!ws.empty() && ws.size() <= 16, "moe: E must be 1..16");
+  std::vector<const void*> p;
+  for (const at::Tensor& w : ws) {
+    check_bf16(w, name);
+    TORCH_CHECK(w.dim() == 2 && w.size(0) == rows && w.size(1) == cols,
+                "moe: every ", name, " must be [", rows, ", ", cols, "]");
+    TORCH_CHECK(w.device() == like.device(), "moe: ", name,
+                " on another device");
+    p.push_back(w.data_ptr());
+  }
+  return p;
+}
+
+}  // namespace
+
+// x [B, H], idx [B, k], wgu E x [2I, H] -> h [B, k, I] with
+// h[b, j] = silu(x[b] @ gate_e^T) * (x[b] @ up_e^T), e = idx[b, j].
+at::Tensor moe_gemv_swiglu(at::Tensor x, at::Tensor idx,
+                           std::vector<at::Tensor> wgu) {
+  check_bf16(x, "x");
+  TORCH_CHECK(x.dim() == 2, "moe_gemv_swiglu: x must be [B, H]");
+  TORCH_CHECK(!wgu.empty() && wgu[0].dim() == 2, "moe_gemv_swiglu: wgu list");
+  const long B = x.size(0), H = x.size(1), I = wgu[0].size(0) / 2;
+  check_moe_routing(idx, x, (long)wgu.size());
+  TORCH_CHECK(idx.size(0) == B, "moe_gemv_swiglu: idx rows must equal B");
+  TORCH_CHECK(H >= 512 && H % 512 == 0 && I >= 512 && I % 512 == 0 &&
+                  2 * I * H < (1L << 31),
+              "moe_gemv_swiglu: H and I must be multiples of 512");
+  auto ptrs = moe_weight_ptrs(wgu, 2 * I, H, x, "wgu");
+  const long k = idx.size(1);
+  auto h = at::empty({B, k, I}, x.options());
+  moe_gemv_swiglu_launch(x.data_ptr(), idx.data_ptr(), ptrs.data(),
+                         h.data_ptr(), (int)B, (int)k, (int)ptrs.size(),
+                         (int)I, (int)H, cur_stream());
+  return h;
+}
+
+// h [B, k, I], idx/cw [B, k], wdown E x [H, I] -> out [B, H] with
+// out[b] = sum_e cw[b, j_e] * (h[b, j_e] @ wdown_e^T), folded in bf16 over
+// ascending e (the bits of the per-expert loop).
+at::Tensor moe_gemv_down_combine(at::Tensor h, at::Tensor idx, at::Tensor cw,
+                                 std::vector<at::Tensor> wdown) {
+  check_bf16(h, "h");
+  check_bf16(cw, "cw");
+  TORCH_CHECK(h.dim() == 3, "moe_gemv_down_combine: h must be [B, k, I]");
+  TORCH_CHECK(!wdown.empty() && wdown[0].dim() == 2,
+              "moe_gemv_down_combine: wdown list");
+  const long B = h.size(0), k = h.size(1), I = h.size(2);
+  const long H = wdown[0].size(0);
+  check_moe_routing(idx, h, (long)wdown.size());
+  TORCH_CHECK(idx.size(0) == B && idx.size(1) == k &&
+                  cw.sizes() == idx.sizes() && cw.device() == h.device(),
+              "moe_gemv_down_combine: idx and cw must be [B, k] like h");
+  TORCH_CHECK(H >= 512 && H % 512 == 0 && I >= 512 && I % 512 == 0 &&
+                  I * H < (1L << 31),
+              "moe_gemv_down_combine: H and I must be multiples of 512");
+  auto ptrs = moe_weight_ptrs(wdown, H, I, h, "wdown");
+  auto out = at::empty({B, H}, h.options());
+  moe_gemv_down_combine_launch(h.data_ptr(), idx.data_ptr(), cw.data_ptr(),
+                               ptrs.data(), out.data_ptr(), (int)B, (int)k,
+                               (int)ptrs.size(), (int)I, (int)H,
+                               cur_stream());
+  return out;
+}
+
 // ---- fused decode rope + cache append -------------------------------------
 // qkv [B, (Hq+2*Hkv)*128] (one position); ropes q/k with cos/sin [S, 64]
 // f32 tables at row `pos` (host int, or device int32 scalar when `pos_dev`
@@ -921,6 +1012,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("decode_attn_dev", &decode_attn_dev);
   m.def("gemv_bf16", &gemv_bf16);
   m.def("gemv_swiglu_bf16", &gemv_swiglu_bf16);
+  m.def("moe_gemv_swiglu", &moe_gemv_swiglu);
+  m.def("moe_gemv_down_combine", &moe_gemv_down_combine);
   m.def("decode_rope_cache", &decode_rope_cache,
         py::arg("qkv"), py::arg("kc"), py::arg("vc"), py::arg("cos"),
         py::arg("sin"), py::arg("pos") = 0,
