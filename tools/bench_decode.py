@@ -68,7 +68,8 @@ def run_batcher(args, model, tokens):
         "pages_in_use": free0 - pb.free_pages(),
         "pages_unshared": B * -(-(S0 + N) // P),
         "batch": B, "prompt": S0, "new_tokens": N,
-        "model": args.model, "dtype": "bf16", "data": "synthetic",
+        "model": args.model, "dtype": "bf16", "weights": args.weights,
+        "data": "synthetic",
         "kv_cache": "paged", "page_size": P, "batcher": True,
         "prefill_chunk": args.prefill_chunk, "shared_prefix": shared,
     }))
@@ -170,7 +171,8 @@ def run_admit_many(args, model, tokens, rounds=5):
         "pages_in_use_after_prefill": pages_prefill,
         "pages_in_use": free0 - pb.free_pages(),
         "batch": B, "prompt": S0, "new_tokens": N,
-        "model": args.model, "dtype": "bf16", "data": "synthetic",
+        "model": args.model, "dtype": "bf16", "weights": args.weights,
+        "data": "synthetic",
         "kv_cache": "paged", "page_size": P, "batcher": True,
         "admit_many": True,
         "prefill_chunk": args.prefill_chunk, "shared_prefix": shared,
@@ -214,6 +216,10 @@ def main():
                         "expert GEMV kernels (fused) or the per-expert loop "
                         "with one host sync per layer (loop); default: "
                         "TORCHX_AMD_MOE_DECODE, else fused")
+    p.add_argument("--weights", choices=["bf16", "fp8"], default="bf16",
+                   help="decode weights of the dense model's block linears: "
+                        "bf16, or fp8 e4m3 rows with an fp32 scale each "
+                        "(W8A16 GEMV kernels; prefill stays bf16)")
     args = p.parse_args()
     if args.moe_decode is not None:
         from torchx_amd import ops
@@ -256,6 +262,14 @@ def main():
         cfg = llama3_8b() if args.model == "llama3_8b" else llama_gpu_tiny()
         torch.manual_seed(0)
         model = LlamaModel(cfg, device=dev)
+    if args.weights == "fp8":
+        if moe:
+            print("--weights fp8 is dense-only (expert weights stay bf16)",
+                  file=sys.stderr)
+            return 1
+        from torchx_amd.models.generate import quantize_decode_weights
+
+        quantize_decode_weights(model)
     B, S0, N = args.batch, args.prompt, args.new
     tokens = torch.randint(0, cfg.vocab_size, (B, S0), device=dev)
     if args.batcher:
@@ -326,7 +340,8 @@ def main():
         "ms_per_decode_step": t_dec / steps * 1e3,
         "prefill_tokens_per_second": B * S0 / t_prefill,
         "batch": B, "prompt": S0, "new_tokens": steps,
-        "model": args.model, "dtype": "bf16", "data": "synthetic", "graphed": bool(args.graph),
+        "model": args.model, "dtype": "bf16", "weights": args.weights,
+        "data": "synthetic", "graphed": bool(args.graph),
         "kv_cache": "paged" if args.paged else "dense",
         "page_size": args.page_size if args.paged else None,
         "moe_decode": ops.get_moe_decode_impl() if moe else None,

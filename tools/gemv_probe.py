@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """Per-shape decode-GEMV probe: gemv_bf16 vs torch.matmul (hipBLASLt) at
 the Llama-3-8B decode shapes, CUDA-event timed, with achieved weight-
-stream GB/s (the op's roof is the ~8 TB/s HBM3E read of W)."""
+stream GB/s (the op's roof is the ~8 TB/s HBM3E read of W); then the
+bf16 kernels against the W8A16 ones (gemv_fp8.hip) on the four block
+shapes at M = 1, 4, 8."""
 
 import os
 import sys
@@ -10,7 +12,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 import torch
 
-from torchx_amd.ops import hip_ops
+from torchx_amd.ops import hip_ops, quantize_fp8_rows
 
 SHAPES = [  # (M, N, K) = (batch, out-features, in-features)
     ("wqkv", 4, 6144, 4096),
@@ -64,7 +66,33 @@ def main():
     print(f"wgu+swiglu fused: {t_f:7.1f} us ({gb/(t_f*1e-6):6.0f} GB/s) "
           f"vs separate gemv {time_fn(lambda: ops.gemv_bf16(x, w)):7.1f} us"
           f" + swiglu kernel")
+    fp8_vs_bf16(dev, ops)
     return 0
+
+
+def fp8_vs_bf16(dev, ops, rounds=3):
+    """bf16 against fp8 weights on the four block GEMVs (wgu through the
+    fused SwiGLU kernels), alternated within each round; median time and
+    weight bytes/s of each, and fp8 time / bf16 time."""
+    print("bf16 vs fp8 weights (us, weight GB/s; ratio = fp8 / bf16 time)")
+    for name, _, N, K in SHAPES[:4]:
+        w = torch.randn(N, K, device=dev, dtype=torch.bfloat16)
+        q = quantize_fp8_rows(w)
+        if name == "wgu":
+            f16, f8 = ops.gemv_swiglu_bf16, ops.gemv_swiglu_fp8w
+        else:
+            f16, f8 = ops.gemv_bf16, ops.gemv_fp8w
+        for M in (1, 4, 8):
+            x = torch.randn(M, K, device=dev, dtype=torch.bfloat16)
+            t16, t8 = [], []
+            for _ in range(rounds):
+                t16.append(time_fn(lambda: f16(x, w)))
+                t8.append(time_fn(lambda: f8(x, q.w8, q.scale)))
+            t16, t8 = sorted(t16)[rounds // 2], sorted(t8)[rounds // 2]
+            print(f"{name:6s} M={M} N={N:6d} K={K:5d}  "
+                  f"bf16 {t16:7.1f} us ({N*K*2/t16/1e3:6.0f} GB/s)  "
+                  f"fp8 {t8:7.1f} us ({N*K/t8/1e3:6.0f} GB/s)  "
+                  f"ratio {t8/t16:.3f}")
 
 
 if __name__ == "__main__":

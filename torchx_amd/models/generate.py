@@ -187,6 +187,33 @@ def _split_qkv(qkv: torch.Tensor, cfg: LlamaConfig):
             v.reshape(B, S, cfg.num_kv_heads, cfg.head_dim).contiguous())
 
 
+def _decode_w(lin):
+    """The weight a decode GEMV of ``lin`` streams: its fp8 copy where
+    ``quantize_decode_weights`` made one, else the bf16 weight."""
+    w8 = getattr(lin, "decode_weight", None)
+    return lin.weight if w8 is None else w8
+
+
+@torch.no_grad()
+def quantize_decode_weights(model, snap_prefill: bool = True):
+    """W8A16 decode: give the four block linears of every LlamaBlock
+    (wqkv, wo, wgu, wdown) an ``ops.Fp8Weight`` copy as ``decode_weight``,
+    which ``decode_step`` then streams in place of the bf16 weight (half
+    the bytes; ops/csrc/gemv_fp8.hip). Prefill keeps the bf16 GEMMs; with
+    ``snap_prefill`` each bf16 weight is overwritten by ``bf16(dequant)``,
+    so that prefill and decode see the same model up to one bf16 rounding
+    of each weight. lm_head and Mixtral expert weights stay bf16."""
+    for blk in model.blocks:
+        if "moe" in blk._modules:  # a MixtralBlock stays bf16 as a whole
+            continue
+        for name in ("wqkv", "wo", "wgu", "wdown"):
+            lin = getattr(blk, name)
+            lin.decode_weight = ops.quantize_fp8_rows(lin.weight)
+            if snap_prefill:
+                lin.weight.copy_(lin.decode_weight.dequant())
+    return model
+
+
 def _mlp_prefill(blk, xn: torch.Tensor) -> torch.Tensor:
     """MLP half of a block in a prefill pass: normed activations in, the
     block's MLP output out. With ``_mlp_decode`` this is all the serving
@@ -205,8 +232,8 @@ def _mlp_decode(blk, xn: torch.Tensor) -> torch.Tensor:
         # generate_moe imports this module
         from .generate_moe import _moe_mlp_decode
         return _moe_mlp_decode(blk.moe, xn)
-    return ops.decode_linear(ops.decode_linear_swiglu(xn, blk.wgu.weight),
-                             blk.wdown.weight)
+    return ops.decode_linear(ops.decode_linear_swiglu(xn, _decode_w(blk.wgu)),
+                             _decode_w(blk.wdown))
 
 
 def _prefill_pass(model, tokens: torch.Tensor, caches: list, start: int,
@@ -397,7 +424,7 @@ def decode_step(model, token: torch.Tensor, caches: list,
     x = model.embed(token).reshape(B, -1)  # [B, H] residual stream
     _, xn = ops.rmsnorm_res(x, None, blocks[0].attn_norm, cfg.rms_eps)
     for i, (blk, cache) in enumerate(zip(blocks, caches)):
-        qkv = ops.decode_linear(xn, blk.wqkv.weight)
+        qkv = ops.decode_linear(xn, _decode_w(blk.wqkv))
         if paged:
             q = ops.paged_decode_rope_cache(
                 qkv, cache.kpool, cache.vpool, cache.block_table,
@@ -414,7 +441,7 @@ def decode_step(model, token: torch.Tensor, caches: list,
                 # scalar pos_dev: hipGraph loop; [B] pos_dev: ragged decode
                 # (continuous batching) — each row attends its own length
                 o = ops.decode_attention_dev(q, cache.k, cache.v, pos_dev)
-        a = ops.decode_linear(o.reshape(B, -1), blk.wo.weight)
+        a = ops.decode_linear(o.reshape(B, -1), _decode_w(blk.wo))
         x, xn = ops.rmsnorm_res(x, a, blk.mlp_norm, cfg.rms_eps)
         m = _mlp_decode(blk, xn)
         w_next = (blocks[i + 1].attn_norm if i + 1 < len(blocks)

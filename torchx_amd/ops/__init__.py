@@ -687,13 +687,69 @@ def decode_rope_cache(qkv: torch.Tensor, kcache: torch.Tensor,
     return q.reshape(B, num_heads, D)
 
 
+# ---------------------------------------------------------------------------
+# W8A16 decode weights: fp8 e4m3 rows with one fp32 scale each, consumed by
+# the gemv_fp8.hip kernels. ``decode_linear`` / ``decode_linear_swiglu``
+# take an ``Fp8Weight`` wherever they take a bf16 weight tensor.
+# ---------------------------------------------------------------------------
+
+FP8_E4M3_MAX = 448.0
+
+
+class Fp8Weight:
+    """A row-scaled fp8 weight: ``w8`` [N, K] float8_e4m3fn and ``scale``
+    [N] fp32; the weight it stands for is ``w8 * scale[:, None]``."""
+
+    def __init__(self, w8: torch.Tensor, scale: torch.Tensor):
+        assert w8.dim() == 2 and w8.dtype == torch.float8_e4m3fn
+        assert scale.dtype == torch.float32 and scale.shape == w8.shape[:1]
+        self.w8 = w8.contiguous()
+        self.scale = scale.contiguous()
+
+    @property
+    def shape(self) -> Tuple[int, int]:
+        return tuple(self.w8.shape)
+
+    def dequant(self) -> torch.Tensor:
+        return self.w8.float() * self.scale[:, None]
+
+    def to(self, device) -> "Fp8Weight":
+        return Fp8Weight(self.w8.to(device), self.scale.to(device))
+
+
+def quantize_fp8_rows(w: torch.Tensor) -> Fp8Weight:
+    """Per-row absmax quantisation of w [N, K] to e4m3: ``scale[n] =
+    amax_k |w[n, k]| / 448`` (1 for a zero row). A load-time one-off in
+    torch. The quotient is clamped to +-448 before the cast: it can pass
+    448 by one fp32 rounding, and the hardware convert turns overflow
+    into NaN (docs/fp8.md)."""
+    wf = w.detach().float()
+    amax = wf.abs().amax(dim=1)
+    scale = torch.where(amax > 0, amax / FP8_E4M3_MAX, torch.ones_like(amax))
+    q = (wf / scale[:, None]).clamp_(-FP8_E4M3_MAX, FP8_E4M3_MAX)
+    return Fp8Weight(q.to(torch.float8_e4m3fn), scale)
+
+
+def _fp8w_kernel_ok(x2: torch.Tensor, w: Fp8Weight) -> bool:
+    """Whether x2 [M, K] bf16 against ``w`` runs on the gemv_fp8.hip
+    kernels (any N: the bf16 path's N <= 32768 rule does not apply)."""
+    M, K = x2.shape
+    return _on_gpu(x2, w.w8, w.scale) and x2.dtype == torch.bfloat16 \
+        and M <= 8 and K % 1024 == 0
+
+
 def decode_linear_swiglu(x: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
     """Fused decode MLP front half: ``silu(x @ gate.T) * (x @ up.T)`` for
     the packed wgu weight ``w = [gate; up]`` [2I, K] — one GEMV-shaped
     dispatch, no [M, 2I] intermediate. Inference only."""
     x2 = x.reshape(-1, x.shape[-1])
     M, K = x2.shape
-    if _on_gpu(x) and M <= 8 and K % 512 == 0 and w.shape[0] % 2 == 0 \
+    if isinstance(w, Fp8Weight):
+        if _fp8w_kernel_ok(x2, w):
+            out = hip_ops().gemv_swiglu_fp8w(x2.contiguous(), w.w8, w.scale)
+        else:
+            out = reference.decode_linear_swiglu_fp8w(x2, w.dequant())
+    elif _on_gpu(x) and M <= 8 and K % 512 == 0 and w.shape[0] % 2 == 0 \
             and w.dtype == torch.bfloat16 and w.is_contiguous():
         out = hip_ops().gemv_swiglu_bf16(x2.contiguous(), w)
     else:
@@ -934,6 +990,12 @@ def decode_linear(x: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
     """
     x2 = x.reshape(-1, x.shape[-1])
     M, K = x2.shape
+    if isinstance(w, Fp8Weight):
+        if _fp8w_kernel_ok(x2, w):
+            out = hip_ops().gemv_fp8w(x2.contiguous(), w.w8, w.scale)
+        else:
+            out = reference.decode_linear_fp8w(x2, w.dequant())
+        return out.reshape(*x.shape[:-1], w.shape[0])
     # N > 32k (lm_head-sized): hipBLASLt's split-K kernels stream W
     # slightly faster there (5.8 vs 5.0 TB/s measured) — route to matmul
     if _on_gpu(x) and M <= 8 and K % 512 == 0 and w.shape[0] <= 32768 \

@@ -144,6 +144,21 @@ def decode_attention(q: torch.Tensor, kcache: torch.Tensor,
     return torch.einsum("bhl,blhd->bhd", p, v).to(q.dtype)
 
 
+def decode_linear_fp8w(x: torch.Tensor, w_deq: torch.Tensor) -> torch.Tensor:
+    """W8A16 decode linear off the kernel path: x [M, K] against the fp32
+    dequantised weight ``w8.float() * scale[:, None]`` [N, K], fp32 math,
+    one rounding to x.dtype."""
+    return (x.float() @ w_deq.t()).to(x.dtype)
+
+
+def decode_linear_swiglu_fp8w(x: torch.Tensor,
+                              w_deq: torch.Tensor) -> torch.Tensor:
+    """``decode_linear_fp8w`` on the packed [gate; up] = [2I, K] weight
+    with SwiGLU in fp32 before the one rounding."""
+    g, u = (x.float() @ w_deq.t()).chunk(2, dim=-1)
+    return (torch.nn.functional.silu(g) * u).to(x.dtype)
+
+
 def paged_gather(pool: torch.Tensor, table_row: torch.Tensor,
                  length: int) -> torch.Tensor:
     """Logical view of one sequence of a paged KV pool: ``pool``
