@@ -3,7 +3,8 @@
 the Llama-3-8B decode shapes, CUDA-event timed, with achieved weight-
 stream GB/s (the op's roof is the ~8 TB/s HBM3E read of W); then the
 bf16 kernels against the W8A16 ones (gemv_fp8.hip) on the four block
-shapes at M = 1, 4, 8."""
+shapes at M = 1, 4, 8. ``--mfma`` runs only the MFMA fp8 kernels
+(gemm_fp8w_mfma.hip) against the dot2 kernels and bf16 matmul."""
 
 import os
 import sys
@@ -95,5 +96,64 @@ def fp8_vs_bf16(dev, ops, rounds=3):
                   f"ratio {t8/t16:.3f}")
 
 
+def _median_rounds(fns, rounds, iters=100):
+    """Median us of each fn over ``rounds`` rounds, the fns alternated
+    within a round."""
+    ts = [[] for _ in fns]
+    for _ in range(rounds):
+        for t, fn in zip(ts, fns):
+            t.append(time_fn(fn, iters))
+    return [sorted(t)[rounds // 2] for t in ts]
+
+
+def mfma_vs_dot2_bf16(dev, ops, rounds=5):
+    """The MFMA fp8-weight kernels (gemm_fp8w_mfma.hip) on the four block
+    shapes (wgu through the fused SwiGLU kernels): against the dot2 kernels
+    at M = 4 .. 8 and against what the bf16 path runs at M = 9, 16, 32
+    (``x @ w.t()``, plus the torch SwiGLU for wgu), alternated within each
+    round, medians. The plain kernel is timed with 1 and with 2 row tiles
+    per block. One timing of the dequantising fallback per shape."""
+    from torchx_amd.ops import reference
+
+    def bf16_swiglu(x, w):
+        g, u = (x @ w.t()).chunk(2, dim=-1)
+        return torch.nn.functional.silu(g.float()).to(u.dtype) * u
+
+    print("mfma fp8 kernels (us, fp8 weight GB/s); rt = row tiles per block")
+    for name, _, N, K in SHAPES[:4]:
+        w = torch.randn(N, K, device=dev, dtype=torch.bfloat16)
+        q = quantize_fp8_rows(w)
+        glu = name == "wgu"
+        if glu:
+            new = [lambda x: ops.gemm_swiglu_fp8w_mfma(x, q.w8, q.scale)]
+            tags = ["mfma"]
+        else:
+            new = [lambda x, rt=rt: ops.gemm_fp8w_mfma(x, q.w8, q.scale, rt)
+                   for rt in (1, 2)]
+            tags = ["mfma rt=1", "mfma rt=2"]
+        for M in (4, 5, 6, 7, 8, 9, 16, 32):
+            x = torch.randn(M, K, device=dev, dtype=torch.bfloat16)
+            if M <= 8:
+                old = ops.gemv_swiglu_fp8w if glu else ops.gemv_fp8w
+                other, otag = (lambda x: old(x, q.w8, q.scale)), "dot2"
+            elif glu:
+                other, otag = (lambda x: bf16_swiglu(x, w)), "bf16 matmul"
+            else:
+                other, otag = (lambda x: x @ w.t()), "bf16 matmul"
+            ts = _median_rounds([lambda f=f: f(x) for f in new + [other]],
+                                rounds)
+            line = "  ".join(f"{tag} {t:7.1f} us ({N*K/t/1e3:6.0f} GB/s)"
+                             for tag, t in zip(tags, ts))
+            print(f"{name:6s} M={M:2d} N={N:6d} K={K:5d}  {line}  "
+                  f"{otag} {ts[-1]:7.1f} us  "
+                  f"ratio {min(ts[:-1])/ts[-1]:.3f}")
+        fb = reference.decode_linear_swiglu_fp8w if glu \
+            else reference.decode_linear_fp8w
+        t = time_fn(lambda: fb(x, q.dequant()), iters=5)
+        print(f"{name:6s} M={M:2d} dequantising fallback {t:9.1f} us")
+
+
 if __name__ == "__main__":
+    if "--mfma" in sys.argv:
+        sys.exit(mfma_vs_dot2_bf16(torch.device("cuda:0"), hip_ops()))
     sys.exit(main())

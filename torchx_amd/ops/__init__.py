@@ -689,7 +689,7 @@ def decode_rope_cache(qkv: torch.Tensor, kcache: torch.Tensor,
 
 # ---------------------------------------------------------------------------
 # W8A16 decode weights: fp8 e4m3 rows with one fp32 scale each, consumed by
-# the gemv_fp8.hip kernels. ``decode_linear`` / ``decode_linear_swiglu``
+# the gemv_fp8.hip and gemm_fp8w_mfma.hip kernels. ``decode_linear`` / ``decode_linear_swiglu``
 # take an ``Fp8Weight`` wherever they take a bf16 weight tensor.
 # ---------------------------------------------------------------------------
 
@@ -730,23 +730,35 @@ def quantize_fp8_rows(w: torch.Tensor) -> Fp8Weight:
     return Fp8Weight(q.to(torch.float8_e4m3fn), scale)
 
 
+# Largest M that the dot2 kernels (gemv_fp8.hip) keep; M above it, up to 32,
+# goes to the MFMA kernels (gemm_fp8w_mfma.hip). Measured on the four
+# llama3-8B block shapes (profiles/README.md r13a): the MFMA kernels are
+# faster on all four at M = 6, 7, 8 (by 2% on wqkv at M = 6, 22-58%
+# elsewhere) and slower on wqkv at M = 4 and 5 (by 24% and 10%).
+FP8W_DOT2_MAX_M = 5
+FP8W_MAX_M = 32
+
+
 def _fp8w_kernel_ok(x2: torch.Tensor, w: Fp8Weight) -> bool:
-    """Whether x2 [M, K] bf16 against ``w`` runs on the gemv_fp8.hip
-    kernels (any N: the bf16 path's N <= 32768 rule does not apply)."""
+    """Whether x2 [M, K] bf16 against ``w`` runs on the fp8-weight kernels
+    (any N: the bf16 path's N <= 32768 rule does not apply)."""
     M, K = x2.shape
     return _on_gpu(x2, w.w8, w.scale) and x2.dtype == torch.bfloat16 \
-        and M <= 8 and K % 1024 == 0
+        and M <= FP8W_MAX_M and K % 1024 == 0
 
 
 def decode_linear_swiglu(x: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
     """Fused decode MLP front half: ``silu(x @ gate.T) * (x @ up.T)`` for
     the packed wgu weight ``w = [gate; up]`` [2I, K] — one GEMV-shaped
-    dispatch, no [M, 2I] intermediate. Inference only."""
+    dispatch, no [M, 2I] intermediate. Inference only. The bf16 kernel
+    takes M <= 8 rows, an ``Fp8Weight`` M <= 32 (see ``decode_linear``)."""
     x2 = x.reshape(-1, x.shape[-1])
     M, K = x2.shape
     if isinstance(w, Fp8Weight):
         if _fp8w_kernel_ok(x2, w):
-            out = hip_ops().gemv_swiglu_fp8w(x2.contiguous(), w.w8, w.scale)
+            fn = hip_ops().gemv_swiglu_fp8w if M <= FP8W_DOT2_MAX_M \
+                else hip_ops().gemm_swiglu_fp8w_mfma
+            out = fn(x2.contiguous(), w.w8, w.scale)
         else:
             out = reference.decode_linear_swiglu_fp8w(x2, w.dequant())
     elif _on_gpu(x) and M <= 8 and K % 512 == 0 and w.shape[0] % 2 == 0 \
@@ -987,12 +999,19 @@ def decode_linear(x: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
     HBM roof at decode batch sizes; this kernel reads each weight byte
     exactly once. Falls back to torch.matmul off-GPU or when the shape
     doesn't qualify (M > 8 or K % 512 != 0). Inference only (no autograd).
+
+    An ``Fp8Weight`` runs on the W8A16 kernels for M <= 32 total rows and
+    K % 1024 == 0, any N: the dot2 GEMV (ops/csrc/gemv_fp8.hip) up to
+    ``FP8W_DOT2_MAX_M`` rows, the MFMA GEMM (ops/csrc/gemm_fp8w_mfma.hip)
+    above. Other shapes dequantise and take the reference path.
     """
     x2 = x.reshape(-1, x.shape[-1])
     M, K = x2.shape
     if isinstance(w, Fp8Weight):
         if _fp8w_kernel_ok(x2, w):
-            out = hip_ops().gemv_fp8w(x2.contiguous(), w.w8, w.scale)
+            fn = hip_ops().gemv_fp8w if M <= FP8W_DOT2_MAX_M \
+                else hip_ops().gemm_fp8w_mfma
+            out = fn(x2.contiguous(), w.w8, w.scale)
         else:
             out = reference.decode_linear_fp8w(x2, w.dequant())
         return out.reshape(*x.shape[:-1], w.shape[0])

@@ -28,18 +28,20 @@ SOURCES = [
     "paged_attn.hip",
     "gemv.hip",
     "gemv_fp8.hip",
+    "gemm_fp8w_mfma.hip",
     "moe_gemv.hip",
     "fp8_cast.hip",
     "probe.hip",
     "bindings.cpp",
 ]
 
-# per-source extra flags: moe_gemv.hip and gemv_fp8.hip keep their fp32
-# arithmetic on the scalar VALU forms (no packed-fp32 instructions)
+# per-source extra flags: moe_gemv.hip and the fp8-weight kernels keep their
+# fp32 arithmetic on the scalar VALU forms (no packed-fp32 instructions)
 _NO_PK_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 EXTRA_FLAGS = {
     "moe_gemv.hip": _NO_PK_F32,
     "gemv_fp8.hip": _NO_PK_F32,
+    "gemm_fp8w_mfma.hip": _NO_PK_F32,
 }
 
 

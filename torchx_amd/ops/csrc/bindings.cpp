@@ -85,6 +85,10 @@ void gemv_fp8w_launch(const void*, const void*, const void*, void*, int, int,
                       int, hipStream_t);
 void gemv_swiglu_fp8w_launch(const void*, const void*, const void*, void*,
                              int, int, int, hipStream_t);
+void gemm_fp8w_mfma_launch(const void*, const void*, const void*, void*, int,
+                           int, int, int, hipStream_t);
+void gemm_swiglu_fp8w_mfma_launch(const void*, const void*, const void*, void*,
+                                  int, int, int, hipStream_t);
 void moe_gemv_swiglu_launch(const void*, const void*, const void* const*,
                             void*, int, int, int, int, int, hipStream_t);
 void moe_gemv_down_combine_launch(const void*, const void*, const void*,
@@ -601,13 +605,14 @@ at::Tensor gemv_swiglu_bf16(at::Tensor x, at::Tensor w) {
   return out;
 }
 
-// ---- W8A16 skinny-M GEMVs (gemv_fp8.hip) -----------------------------------
+// ---- W8A16 skinny-M GEMVs (gemv_fp8.hip, gemm_fp8w_mfma.hip) ---------------
 // x [M, K] bf16, w8 [N, K] float8_e4m3fn, scale [N] f32 (one per row of w8)
 // -> bf16(scale[n] * x @ w8.T), resp. its SwiGLU over the packed [2I, K].
+// The dot2 kernels take M <= 8, the MFMA ones M <= 32.
 namespace {
 
 void check_fp8w(const at::Tensor& x, const at::Tensor& w8,
-                const at::Tensor& scale, const char* op) {
+                const at::Tensor& scale, const char* op, long max_m) {
   check_bf16(x, "x");
   check_f32(scale, "scale");
   TORCH_CHECK(w8.is_cuda(), op, ": w8 must be on GPU");
@@ -615,7 +620,8 @@ void check_fp8w(const at::Tensor& x, const at::Tensor& w8,
               ": w8 must be float8_e4m3fn");
   TORCH_CHECK(w8.is_contiguous(), op, ": w8 must be contiguous");
   TORCH_CHECK(x.dim() == 2 && w8.dim() == 2, op, ": 2D only");
-  TORCH_CHECK(x.size(0) >= 1 && x.size(0) <= 8, op, ": M must be 1..8");
+  TORCH_CHECK(x.size(0) >= 1 && x.size(0) <= max_m, op, ": M must be 1..",
+              max_m);
   TORCH_CHECK(w8.size(1) == x.size(1), op, ": K mismatch");
   TORCH_CHECK(x.size(1) % 1024 == 0, op, ": K must be a multiple of 1024");
   TORCH_CHECK(scale.numel() == w8.size(0), op, ": one scale per row of w8");
@@ -624,7 +630,7 @@ void check_fp8w(const at::Tensor& x, const at::Tensor& w8,
 }  // namespace
 
 at::Tensor gemv_fp8w(at::Tensor x, at::Tensor w8, at::Tensor scale) {
-  check_fp8w(x, w8, scale, "gemv_fp8w");
+  check_fp8w(x, w8, scale, "gemv_fp8w", 8);
   const long M = x.size(0), K = x.size(1), N = w8.size(0);
   auto out = at::empty({M, N}, x.options());
   gemv_fp8w_launch(x.data_ptr(), w8.data_ptr(), scale.data_ptr(),
@@ -633,13 +639,40 @@ at::Tensor gemv_fp8w(at::Tensor x, at::Tensor w8, at::Tensor scale) {
 }
 
 at::Tensor gemv_swiglu_fp8w(at::Tensor x, at::Tensor w8, at::Tensor scale) {
-  check_fp8w(x, w8, scale, "gemv_swiglu_fp8w");
+  check_fp8w(x, w8, scale, "gemv_swiglu_fp8w", 8);
   const long M = x.size(0), K = x.size(1), I = w8.size(0) / 2;
   TORCH_CHECK(I >= 1 && w8.size(0) == 2 * I, "gemv_swiglu_fp8w: w8 is [2I, K]");
   auto out = at::empty({M, I}, x.options());
   gemv_swiglu_fp8w_launch(x.data_ptr(), w8.data_ptr(), scale.data_ptr(),
                           out.data_ptr(), (int)M, (int)I, (int)K,
                           cur_stream());
+  return out;
+}
+
+// rt = 1 or 2 forces the row tiles per block (tools/gemv_probe.py), 0
+// leaves the choice to the launcher
+at::Tensor gemm_fp8w_mfma(at::Tensor x, at::Tensor w8, at::Tensor scale,
+                          int64_t rt) {
+  check_fp8w(x, w8, scale, "gemm_fp8w_mfma", 32);
+  TORCH_CHECK(rt >= 0 && rt <= 2, "gemm_fp8w_mfma: rt must be 0, 1 or 2");
+  const long M = x.size(0), K = x.size(1), N = w8.size(0);
+  auto out = at::empty({M, N}, x.options());
+  gemm_fp8w_mfma_launch(x.data_ptr(), w8.data_ptr(), scale.data_ptr(),
+                        out.data_ptr(), (int)M, (int)N, (int)K, (int)rt,
+                        cur_stream());
+  return out;
+}
+
+at::Tensor gemm_swiglu_fp8w_mfma(at::Tensor x, at::Tensor w8,
+                                 at::Tensor scale) {
+  check_fp8w(x, w8, scale, "gemm_swiglu_fp8w_mfma", 32);
+  const long M = x.size(0), K = x.size(1), I = w8.size(0) / 2;
+  TORCH_CHECK(I >= 1 && w8.size(0) == 2 * I,
+              "gemm_swiglu_fp8w_mfma: w8 is [2I, K]");
+  auto out = at::empty({M, I}, x.options());
+  gemm_swiglu_fp8w_mfma_launch(x.data_ptr(), w8.data_ptr(), scale.data_ptr(),
+                               out.data_ptr(), (int)M, (int)I, (int)K,
+                               cur_stream());
   return out;
 }
 
@@ -1060,6 +1093,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gemv_swiglu_bf16", &gemv_swiglu_bf16);
   m.def("gemv_fp8w", &gemv_fp8w);
   m.def("gemv_swiglu_fp8w", &gemv_swiglu_fp8w);
+  m.def("gemm_fp8w_mfma", &gemm_fp8w_mfma, py::arg("x"), py::arg("w8"),
+        py::arg("scale"), py::arg("rt") = 0);
+  m.def("gemm_swiglu_fp8w_mfma", &gemm_swiglu_fp8w_mfma);
   m.def("moe_gemv_swiglu", &moe_gemv_swiglu);
   m.def("moe_gemv_down_combine", &moe_gemv_down_combine);
   m.def("decode_rope_cache", &decode_rope_cache,
