@@ -217,9 +217,10 @@ def main():
                         "with one host sync per layer (loop); default: "
                         "TORCHX_AMD_MOE_DECODE, else fused")
     p.add_argument("--weights", choices=["bf16", "fp8"], default="bf16",
-                   help="decode weights of the dense model's block linears: "
-                        "bf16, or fp8 e4m3 rows with an fp32 scale each "
-                        "(W8A16 GEMV kernels; prefill stays bf16)")
+                   help="decode weights of the block linears (Mixtral: "
+                        "attention linears and experts): bf16, or fp8 e4m3 "
+                        "rows with an fp32 scale each (W8A16 GEMV kernels; "
+                        "prefill stays bf16)")
     args = p.parse_args()
     if args.moe_decode is not None:
         from torchx_amd import ops
@@ -263,10 +264,6 @@ def main():
         torch.manual_seed(0)
         model = LlamaModel(cfg, device=dev)
     if args.weights == "fp8":
-        if moe:
-            print("--weights fp8 is dense-only (expert weights stay bf16)",
-                  file=sys.stderr)
-            return 1
         from torchx_amd.models.generate import quantize_decode_weights
 
         quantize_decode_weights(model)

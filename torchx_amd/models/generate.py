@@ -199,15 +199,23 @@ def quantize_decode_weights(model, snap_prefill: bool = True):
     """W8A16 decode: give the four block linears of every LlamaBlock
     (wqkv, wo, wgu, wdown) an ``ops.Fp8Weight`` copy as ``decode_weight``,
     which ``decode_step`` then streams in place of the bf16 weight (half
-    the bytes; ops/csrc/gemv_fp8.hip). Prefill keeps the bf16 GEMMs; with
-    ``snap_prefill`` each bf16 weight is overwritten by ``bf16(dequant)``,
-    so that prefill and decode see the same model up to one bf16 rounding
-    of each weight. lm_head and Mixtral expert weights stay bf16."""
+    the bytes; ops/csrc/gemv_fp8.hip). A MixtralBlock gets one for wqkv
+    and wo and for every local expert's wgu and wdown, which the grouped
+    expert kernels stream (ops/csrc/moe_gemv_fp8.hip). Prefill keeps the
+    bf16 GEMMs; with ``snap_prefill`` each bf16 weight is overwritten by
+    ``bf16(dequant)``, so that prefill and decode see the same model up to
+    one bf16 rounding of each weight. lm_head and the Mixtral router stay
+    bf16."""
     for blk in model.blocks:
-        if "moe" in blk._modules:  # a MixtralBlock stays bf16 as a whole
-            continue
-        for name in ("wqkv", "wo", "wgu", "wdown"):
-            lin = getattr(blk, name)
+        lins = [blk.wqkv, blk.wo]
+        if "moe" in blk._modules:
+            for ex in blk.moe.local_experts:
+                lins += [ex.wgu, ex.wdown]
+            # the layer's cached decode weight lists are stale now
+            blk.moe.__dict__.pop("_decode_weights", None)
+        else:
+            lins += [blk.wgu, blk.wdown]
+        for lin in lins:
             lin.decode_weight = ops.quantize_fp8_rows(lin.weight)
             if snap_prefill:
                 lin.weight.copy_(lin.decode_weight.dequant())

@@ -31,7 +31,8 @@ import torch
 from torchx_amd import ops
 
 from .generate import (
-    KVCache, decode_step, generate, prefill, prefill_extend, prefill_ragged,
+    KVCache, _decode_w, decode_step, generate, prefill, prefill_extend,
+    prefill_ragged,
 )
 from .mixtral import MoELayer
 
@@ -42,13 +43,17 @@ __all__ = ["prefill_moe", "prefill_extend_moe", "prefill_ragged_moe",
 def _expert_weights(moe: MoELayer):
     """The experts' (wgu, wdown) weight lists, built once per layer. They
     hold the parameters themselves (no copy, no stacking), which ``.to()``
-    and ``load_state_dict`` update in place."""
+    and ``load_state_dict`` update in place — or the experts' fp8
+    ``decode_weight`` where ``quantize_decode_weights`` made them; it drops
+    the cached lists, and so does a change in whether the experts have
+    one."""
+    fp8 = hasattr(moe.local_experts[0].wgu, "decode_weight")
     cached = moe.__dict__.get("_decode_weights")
-    if cached is None:
-        cached = ([e.wgu.weight for e in moe.local_experts],
-                  [e.wdown.weight for e in moe.local_experts])
+    if cached is None or cached[0] != fp8:
+        cached = (fp8, [_decode_w(e.wgu) for e in moe.local_experts],
+                  [_decode_w(e.wdown) for e in moe.local_experts])
         moe.__dict__["_decode_weights"] = cached
-    return cached
+    return cached[1:]
 
 
 def _moe_mlp_decode(moe: MoELayer, x: torch.Tensor) -> torch.Tensor:

@@ -1085,15 +1085,24 @@ def _moe_fused_ok(x, idx, cw, wgu, wdown) -> bool:
             or not 1 <= idx.shape[1] <= min(8, E) \
             or cw.shape != idx.shape or cw.dtype != torch.bfloat16:
         return False
+    # all-bf16 or all-Fp8Weight experts; a mixed list takes the loop
+    fp8 = isinstance(wgu[0], Fp8Weight)
+    if any(isinstance(w, Fp8Weight) != fp8 for w in (*wgu, *wdown)):
+        return False
     two_i = wgu[0].shape[0]
     I = two_i // 2
-    if two_i % 2 or H % 512 or I % 512 or H == 0 or I == 0 \
+    tile = 1024 if fp8 else 512
+    if two_i % 2 or H % tile or I % tile or H == 0 or I == 0 \
             or two_i * H >= 2 ** 31:
         return False
-    return all(w.dtype == torch.bfloat16 and w.is_contiguous()
-               and w.device == x.device
-               for w in (*wgu, *wdown)) \
-        and all(w.shape == (two_i, H) for w in wgu) \
+    if fp8:  # Fp8Weight keeps w8 and scale contiguous, e4m3 and fp32
+        if not all(w.w8.device == x.device and w.scale.device == x.device
+                   for w in (*wgu, *wdown)):
+            return False
+    elif not all(w.dtype == torch.bfloat16 and w.is_contiguous()
+                 and w.device == x.device for w in (*wgu, *wdown)):
+        return False
+    return all(w.shape == (two_i, H) for w in wgu) \
         and all(w.shape == (H, I) for w in wdown)
 
 
@@ -1105,16 +1114,27 @@ def moe_decode_mlp(x: torch.Tensor, idx: torch.Tensor, cw: torch.Tensor,
     (the experts of a row distinct), ``wgu`` / ``wdown`` the E experts'
     packed gate|up [2I, H] and down [H, I] weights (separate tensors, never
     stacked) -> ``out[b] = sum_j cw[b, j] * down_e(swiglu(wgu_e x[b]))``,
-    e = idx[b, j], [B, H] bf16. Inference only.
+    e = idx[b, j], [B, H] bf16. Inference only. The experts may also all
+    be ``Fp8Weight``s (W8A16, ops/csrc/moe_gemv_fp8.hip).
 
-    On the GPU with B <= 8, k <= 8, E <= 16 and H, I multiples of 512 this
-    is two dispatches (``moe_gemv_swiglu``, ``moe_gemv_down_combine``) and
-    no host sync; everything else (CPU, larger batches, other shapes, or
-    ``set_moe_decode_impl("loop")``) runs ``moe_decode_mlp_loop``, whose
-    bits the kernels reproduce."""
+    On the GPU with B <= 8, k <= 8, E <= 16 and H, I multiples of 512
+    (1024 for ``Fp8Weight`` experts) this is two dispatches
+    (``moe_gemv_swiglu``, ``moe_gemv_down_combine`` or their ``_fp8w``
+    forms) and no host sync; everything else (CPU, larger batches, other
+    shapes, lists that mix bf16 and fp8 experts, or
+    ``set_moe_decode_impl("loop")``) runs ``moe_decode_mlp_loop``. The
+    kernels reproduce its bits; with ``Fp8Weight`` experts they do so
+    where the loop runs the dot2 GEMVs (groups of up to
+    ``FP8W_DOT2_MAX_M`` tokens), and differ in the last bits from the
+    MFMA kernels it takes above."""
     if _moe_decode_impl == "fused" and _moe_fused_ok(x, idx, cw, wgu, wdown):
         hip = hip_ops()
-        idx, wgu, wdown = idx.contiguous(), list(wgu), list(wdown)
-        h = hip.moe_gemv_swiglu(x.contiguous(), idx, wgu)
-        return hip.moe_gemv_down_combine(h, idx, cw.contiguous(), wdown)
+        x, idx, cw = x.contiguous(), idx.contiguous(), cw.contiguous()
+        if isinstance(wgu[0], Fp8Weight):
+            h = hip.moe_gemv_swiglu_fp8w(x, idx, [w.w8 for w in wgu],
+                                         [w.scale for w in wgu])
+            return hip.moe_gemv_down_combine_fp8w(
+                h, idx, cw, [w.w8 for w in wdown], [w.scale for w in wdown])
+        h = hip.moe_gemv_swiglu(x, idx, list(wgu))
+        return hip.moe_gemv_down_combine(h, idx, cw, list(wdown))
     return moe_decode_mlp_loop(x, idx, cw, wgu, wdown)

@@ -30,6 +30,7 @@ SOURCES = [
     "gemv_fp8.hip",
     "gemm_fp8w_mfma.hip",
     "moe_gemv.hip",
+    "moe_gemv_fp8.hip",
     "fp8_cast.hip",
     "probe.hip",
     "bindings.cpp",
@@ -40,6 +41,7 @@ SOURCES = [
 _NO_PK_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 EXTRA_FLAGS = {
     "moe_gemv.hip": _NO_PK_F32,
+    "moe_gemv_fp8.hip": _NO_PK_F32,
     "gemv_fp8.hip": _NO_PK_F32,
     "gemm_fp8w_mfma.hip": _NO_PK_F32,
 }

@@ -94,6 +94,13 @@ void moe_gemv_swiglu_launch(const void*, const void*, const void* const*,
 void moe_gemv_down_combine_launch(const void*, const void*, const void*,
                                   const void* const*, void*, int, int, int,
                                   int, int, hipStream_t);
+void moe_gemv_swiglu_fp8w_launch(const void*, const void*, const void* const*,
+                                 const void* const*, void*, int, int, int,
+                                 int, int, hipStream_t);
+void moe_gemv_down_combine_fp8w_launch(const void*, const void*, const void*,
+                                       const void* const*, const void* const*,
+                                       void*, int, int, int, int, int, int,
+                                       hipStream_t);
 }
 
 namespace {
@@ -762,6 +769,102 @@ at::Tensor moe_gemv_down_combine(at::Tensor h, at::Tensor idx, at::Tensor cw,
   return out;
 }
 
+// ---- W8A16 device-routed MoE decode MLP (moe_gemv_fp8.hip) ------------------
+// The bf16 pair above on ops.Fp8Weight experts: every expert is a w8
+// [rows, cols] float8_e4m3fn tensor and a scale [rows] f32 tensor, both
+// lists' base pointers go to the kernel by value.
+namespace {
+
+struct MoeFp8Ptrs {
+  std::vector<const void*> w8, scale;
+};
+
+MoeFp8Ptrs moe_fp8_weight_ptrs(const std::vector<at::Tensor>& w8s,
+                               const std::vector<at::Tensor>& scales,
+                               long rows, long cols, const at::Tensor& like,
+                               const char* name) {
+  TORCH_CHECK(!w8s.empty() && w8s.size() <= 16, "moe: E must be 1..16");
+  TORCH_CHECK(scales.size() == w8s.size(), "moe: one scale tensor per ", name);
+  MoeFp8Ptrs p;
+  for (size_t e = 0; e < w8s.size(); ++e) {
+    const at::Tensor& w = w8s[e];
+    const at::Tensor& s = scales[e];
+    TORCH_CHECK(w.is_cuda() && w.scalar_type() == at::kFloat8_e4m3fn &&
+                    w.is_contiguous(),
+                "moe: every ", name,
+                " must be a contiguous float8_e4m3fn device tensor");
+    TORCH_CHECK(w.dim() == 2 && w.size(0) == rows && w.size(1) == cols,
+                "moe: every ", name, " must be [", rows, ", ", cols, "]");
+    check_f32(s, "scale");
+    TORCH_CHECK(s.dim() == 1 && s.size(0) == rows, "moe: every ", name,
+                " scale must be [", rows, "]");
+    TORCH_CHECK(w.device() == like.device() && s.device() == like.device(),
+                "moe: ", name, " on another device");
+    p.w8.push_back(w.data_ptr());
+    p.scale.push_back(s.data_ptr());
+  }
+  return p;
+}
+
+}  // namespace
+
+// x [B, H], idx [B, k], E x (w8 [2I, H], scale [2I]) -> h [B, k, I]
+at::Tensor moe_gemv_swiglu_fp8w(at::Tensor x, at::Tensor idx,
+                                std::vector<at::Tensor> w8,
+                                std::vector<at::Tensor> scale) {
+  check_bf16(x, "x");
+  TORCH_CHECK(x.dim() == 2, "moe_gemv_swiglu_fp8w: x must be [B, H]");
+  TORCH_CHECK(!w8.empty() && w8[0].dim() == 2,
+              "moe_gemv_swiglu_fp8w: w8 list");
+  const long B = x.size(0), H = x.size(1), I = w8[0].size(0) / 2;
+  check_moe_routing(idx, x, (long)w8.size());
+  TORCH_CHECK(idx.size(0) == B, "moe_gemv_swiglu_fp8w: idx rows must equal B");
+  TORCH_CHECK(H >= 1024 && H % 1024 == 0 && I >= 1024 && I % 1024 == 0 &&
+                  2 * I * H < (1L << 31),
+              "moe_gemv_swiglu_fp8w: H and I must be multiples of 1024");
+  auto p = moe_fp8_weight_ptrs(w8, scale, 2 * I, H, x, "wgu");
+  const long k = idx.size(1);
+  auto h = at::empty({B, k, I}, x.options());
+  moe_gemv_swiglu_fp8w_launch(x.data_ptr(), idx.data_ptr(), p.w8.data(),
+                              p.scale.data(), h.data_ptr(), (int)B, (int)k,
+                              (int)p.w8.size(), (int)I, (int)H, cur_stream());
+  return h;
+}
+
+// h [B, k, I], idx/cw [B, k], E x (w8 [H, I], scale [H]) -> out [B, H].
+// rows = 2 or 4 forces the output rows per wave (tools/moe_probe.py), 0
+// leaves the choice to the launcher.
+at::Tensor moe_gemv_down_combine_fp8w(at::Tensor h, at::Tensor idx,
+                                      at::Tensor cw,
+                                      std::vector<at::Tensor> w8,
+                                      std::vector<at::Tensor> scale,
+                                      int64_t rows) {
+  check_bf16(h, "h");
+  check_bf16(cw, "cw");
+  TORCH_CHECK(h.dim() == 3, "moe_gemv_down_combine_fp8w: h must be [B, k, I]");
+  TORCH_CHECK(!w8.empty() && w8[0].dim() == 2,
+              "moe_gemv_down_combine_fp8w: w8 list");
+  TORCH_CHECK(rows == 0 || rows == 2 || rows == 4,
+              "moe_gemv_down_combine_fp8w: rows must be 0, 2 or 4");
+  const long B = h.size(0), k = h.size(1), I = h.size(2);
+  const long H = w8[0].size(0);
+  check_moe_routing(idx, h, (long)w8.size());
+  TORCH_CHECK(idx.size(0) == B && idx.size(1) == k &&
+                  cw.sizes() == idx.sizes() && cw.device() == h.device() &&
+                  cw.is_contiguous(),
+              "moe_gemv_down_combine_fp8w: idx and cw must be [B, k] like h");
+  TORCH_CHECK(H >= 1024 && H % 1024 == 0 && I >= 1024 && I % 1024 == 0 &&
+                  I * H < (1L << 31),
+              "moe_gemv_down_combine_fp8w: H and I must be multiples of 1024");
+  auto p = moe_fp8_weight_ptrs(w8, scale, H, I, h, "wdown");
+  auto out = at::empty({B, H}, h.options());
+  moe_gemv_down_combine_fp8w_launch(
+      h.data_ptr(), idx.data_ptr(), cw.data_ptr(), p.w8.data(),
+      p.scale.data(), out.data_ptr(), (int)B, (int)k, (int)p.w8.size(),
+      (int)I, (int)H, (int)rows, cur_stream());
+  return out;
+}
+
 // ---- fused decode rope + cache append -------------------------------------
 // qkv [B, (Hq+2*Hkv)*128] (one position); ropes q/k with cos/sin [S, 64]
 // f32 tables at row `pos` (host int, or device int32 scalar when `pos_dev`
@@ -1098,6 +1201,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gemm_swiglu_fp8w_mfma", &gemm_swiglu_fp8w_mfma);
   m.def("moe_gemv_swiglu", &moe_gemv_swiglu);
   m.def("moe_gemv_down_combine", &moe_gemv_down_combine);
+  m.def("moe_gemv_swiglu_fp8w", &moe_gemv_swiglu_fp8w);
+  m.def("moe_gemv_down_combine_fp8w", &moe_gemv_down_combine_fp8w,
+        py::arg("h"), py::arg("idx"), py::arg("cw"), py::arg("w8"),
+        py::arg("scale"), py::arg("rows") = 0);
   m.def("decode_rope_cache", &decode_rope_cache,
         py::arg("qkv"), py::arg("kc"), py::arg("vc"), py::arg("cos"),
         py::arg("sin"), py::arg("pos") = 0,
