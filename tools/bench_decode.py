@@ -221,7 +221,15 @@ def main():
                         "attention linears and experts): bf16, or fp8 e4m3 "
                         "rows with an fp32 scale each (W8A16 GEMV kernels; "
                         "prefill stays bf16)")
+    p.add_argument("--kv-cache", choices=["bf16", "fp8"], default="bf16",
+                   help="dense KV cache: bf16, or fp8 e4m3 rows with an fp32 "
+                        "scale per (token, kv head) (decode_attn_fp8kv.hip; "
+                        "not with --paged)")
     args = p.parse_args()
+    if args.kv_cache == "fp8" and args.paged:
+        print("--kv-cache fp8 is dense-only (the paged pools are bf16)",
+              file=sys.stderr)
+        return 1
     if args.moe_decode is not None:
         from torchx_amd import ops
 
@@ -240,7 +248,7 @@ def main():
 
     from torchx_amd import ops
     from torchx_amd.models.generate import (
-        KVCache, PagedKVCache, decode_step, prefill,
+        Fp8KVCache, KVCache, PagedKVCache, decode_step, prefill,
     )
     from torchx_amd.models.llama import LlamaModel, llama3_8b, llama_gpu_tiny
 
@@ -291,7 +299,8 @@ def main():
             pos.add_(1)
             return logits
     else:
-        caches = [KVCache.empty(cfg, B, S0 + N + 8, dev)
+        kind = Fp8KVCache if args.kv_cache == "fp8" else KVCache
+        caches = [kind.empty(cfg, B, S0 + N + 8, dev)
                   for _ in range(cfg.num_layers)]
 
     # warm prefill once (hipBLASLt algo selection etc.), then re-time it
@@ -340,6 +349,7 @@ def main():
         "model": args.model, "dtype": "bf16", "weights": args.weights,
         "data": "synthetic", "graphed": bool(args.graph),
         "kv_cache": "paged" if args.paged else "dense",
+        "kv_dtype": args.kv_cache,
         "page_size": args.page_size if args.paged else None,
         "moe_decode": ops.get_moe_decode_impl() if moe else None,
     }))

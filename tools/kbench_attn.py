@@ -252,6 +252,73 @@ def bench_fwd_map(B, S, Hq, Hkv, iters, rounds=5):
           f"{fl / res['balanced'][0] / 1e9:.0f} TF/s)", res, "legacy")
 
 
+def bench_decode(iters, rounds=5, Bs=(1, 4, 8), Ls=(512, 4096, 32768),
+                 splits=(4, 8, 16, 32)):
+    """Decode attention over a bf16 cache (decode_attn_split + merge)
+    against the fp8 cache kernels (decode_attn_fp8kv split + merge) on the
+    same logical cache, H32/8: the fp8 cache is the bf16 one quantised by
+    ops.quantize_kv_rows. Per shape the candidates — bf16, fp8 under the
+    launcher's split policy, fp8 with the QK product in the fp32 convert
+    form, fp8 at each forced split — alternate within
+    every round; median and [min..max] over the rounds, by device events.
+    Every call reads another of several cache copies (about 1 GiB of bf16
+    in all), as the layers of a model do, so that no candidate is served
+    from a cache the previous call filled. The bytes are the unique K/V
+    (and scale) bytes of one call."""
+    dev = torch.device("cuda", 0)
+    Hq, Hkv, D = 32, 8, 128
+    for B in Bs:
+        for L in Ls:
+            torch.manual_seed(0)
+            by16 = B * L * Hkv * D * 2 * 2
+            by8 = B * L * Hkv * (D + 4) * 2
+            copies = max(1, min(16, (1 << 30) // by16))
+            q = torch.randn(B, Hq, D, device=dev, dtype=torch.bfloat16)
+            c16, c8 = [], []
+            for _ in range(copies):
+                k = torch.randn(B, L, Hkv, D, device=dev,
+                                dtype=torch.bfloat16)
+                v = torch.randn_like(k)
+                c16.append((k, v))
+                k8, ks = ops.quantize_kv_rows(k)
+                v8, vs = ops.quantize_kv_rows(v)
+                c8.append((k8, v8, ks, vs))
+            turn = {"i": 0}
+
+            def nxt(caches):
+                turn["i"] = (turn["i"] + 1) % copies
+                return caches[turn["i"]]
+
+            def bf16():
+                return ops.decode_attention(q, *nxt(c16), L)
+
+            def fp8(split=None):
+                return lambda: ops.decode_attention_fp8kv(
+                    q, *nxt(c8), L, split=split)
+
+            def fp8_f32():
+                # the fp32 convert form of the QK product (not what the
+                # ops run): raw extension call
+                return ops.hip_ops().decode_attn_fp8kv(
+                    q, *nxt(c8), L, None, D ** -0.5, 0, False)
+
+            turn["i"] = 0
+            a = fp8()().float()
+            turn["i"] = 0
+            diff = (fp8_f32().float() - a).abs().max().item()
+            fns = {"bf16": bf16, "fp8": fp8(), "fp8_f32": fp8_f32}
+            fns.update({f"fp8_s{sp}": fp8(sp) for sp in splits})
+            n = iters * (50 if L <= 4096 else 5)
+            res = _alternate(fns, n, rounds)
+            _show(f"decode B{B} L{L} H{Hq}/{Hkv} copies {copies} "
+                  f"max|dot2 - fp32 form| {diff:.3g} "
+                  f"(bf16 {by16 / res['bf16'][0] / 1e9:.2f} TB/s of "
+                  f"{by16 / 2 ** 20:.1f} MiB, fp8 "
+                  f"{by8 / res['fp8'][0] / 1e9:.2f} TB/s of "
+                  f"{by8 / 2 ** 20:.1f} MiB)", res, "bf16")
+            del c16, c8
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--B", type=int, default=4)
@@ -261,7 +328,7 @@ def main():
     p.add_argument("--iters", type=int, default=20)
     p.add_argument("--mode", type=str, default="both",
                    choices=["fwd", "bwd", "both", "fwd-map", "paged-prefill",
-                            "paged-prefill-ragged"],
+                            "paged-prefill-ragged", "decode"],
                    help="fwd-map: time attn_fwd at --B/--S/--Hq/--Hkv "
                         "under each block map (ops.set_attn_fwd_map) in "
                         "one process; paged-prefill: time paged_prefill_attn at ctx=0 "
@@ -270,7 +337,10 @@ def main():
                         "paged-prefill-ragged: time the ragged kernel "
                         "against paged_prefill_attn at equal and mixed "
                         "lengths, and the fused rope + page append against "
-                        "the dispatches it replaces")
+                        "the dispatches it replaces; decode: time decode "
+                        "attention over a bf16 and over an fp8 KV cache "
+                        "(B 1/4/8 x L 512/4096/32768, H32/8), with the fp8 "
+                        "split sweep")
     p.add_argument("--dq-mode", type=str, default=None,
                    choices=["stream", "recompute"],
                    help="dQ path of the backward (default: the extension's "
@@ -283,6 +353,9 @@ def main():
     args = p.parse_args()
     if args.mode == "paged-prefill":
         bench_paged_prefill(args.iters)
+        return
+    if args.mode == "decode":
+        bench_decode(args.iters)
         return
     if args.mode == "paged-prefill-ragged":
         bench_paged_prefill_ragged(args.iters)

@@ -46,6 +46,49 @@ class KVCache:
         )
 
 
+@dataclass
+class Fp8KVCache:
+    """One layer's dense KV cache in fp8 (OCP e4m3) with one fp32 scale per
+    (token, kv head): the cached value is ``k8 * ks[..., None]``. 4 KB + 64 B
+    per Llama-3-8B token-row against the bf16 cache's 8 KB. Filled by
+    ``ops.kv_quantize_store`` (prefill) and ``ops.decode_rope_cache_fp8kv``
+    (decode), read by ``ops.decode_attention_fp8kv``."""
+    k8: torch.Tensor  # [B, T, Hkv, 128] float8_e4m3fn
+    v8: torch.Tensor
+    ks: torch.Tensor  # [B, T, Hkv] fp32
+    vs: torch.Tensor
+    length: int = 0
+
+    @staticmethod
+    def empty(cfg: LlamaConfig, batch: int, max_len: int,
+              device: torch.device) -> "Fp8KVCache":
+        shape = (batch, max_len, cfg.num_kv_heads, cfg.head_dim)
+        return Fp8KVCache(
+            k8=torch.zeros(shape, dtype=torch.float8_e4m3fn, device=device),
+            v8=torch.zeros(shape, dtype=torch.float8_e4m3fn, device=device),
+            ks=torch.ones(shape[:3], dtype=torch.float32, device=device),
+            vs=torch.ones(shape[:3], dtype=torch.float32, device=device),
+        )
+
+    def for_row(self, row: int) -> "Fp8KVCache":
+        """Views of one batch row, for a [1, S] prefill."""
+        r = slice(row, row + 1)
+        return Fp8KVCache(self.k8[r], self.v8[r], self.ks[r], self.vs[r])
+
+
+KV_CACHE_KINDS = ("bf16", "fp8")
+
+
+def _dense_caches(kv_cache: str, cfg: LlamaConfig, batch: int, max_len: int,
+                  device: torch.device) -> list:
+    """Per-layer dense caches of the kind ``kv_cache`` names."""
+    assert kv_cache in KV_CACHE_KINDS, \
+        f"kv_cache must be one of {KV_CACHE_KINDS}, got {kv_cache!r}"
+    kind = Fp8KVCache if kv_cache == "fp8" else KVCache
+    return [kind.empty(cfg, batch, max_len, device)
+            for _ in range(cfg.num_layers)]
+
+
 class OutOfPages(RuntimeError):
     """The page pool cannot supply the pages a request needs."""
 
@@ -272,13 +315,18 @@ def _prefill_pass(model, tokens: torch.Tensor, caches: list, start: int,
 @torch.no_grad()
 def prefill(model, tokens: torch.Tensor, caches: list) -> torch.Tensor:
     """Run the prompt through the model (Llama or Mixtral), filling
-    per-layer KV caches of either kind; attention is the dense training
-    kernel. Returns the last position's logits [B, vocab]."""
+    per-layer KV caches of any kind; attention is the dense training
+    kernel on the fresh bf16 k/v (an ``Fp8KVCache`` only stores their
+    quantised rows). Returns the last position's logits [B, vocab]."""
     S = tokens.shape[1]
 
     def attend(cache, q, k, v):
         if isinstance(cache, PagedKVCache):
             cache.store_prefix(k, v)
+        elif isinstance(cache, Fp8KVCache):
+            ops.kv_quantize_store(k, v, cache.k8, cache.v8, cache.ks,
+                                  cache.vs, 0)
+            cache.length = S
         else:
             cache.k[:, :S] = k
             cache.v[:, :S] = v
@@ -418,11 +466,14 @@ def decode_step(model, token: torch.Tensor, caches: list,
     kernels (see PagedBatcher). A Mixtral model runs the same step with
     its active-expert MLP half (``_mlp_decode``), which is
     position-independent; its routing reads the device, so only the
-    dense model's step is capturable."""
+    dense model's step is capturable. ``Fp8KVCache`` caches take all three
+    ``pos`` forms through the fp8 KV kernels (quantising append, GQA-shared
+    attention)."""
     cfg = model.cfg
     B = token.shape[0]
     blocks = model.blocks
     paged = isinstance(caches[0], PagedKVCache)
+    fp8kv = isinstance(caches[0], Fp8KVCache)
     if paged:
         assert pos_dev is not None and pos_dev.numel() == B, \
             "paged caches need an int32 [B] pos_dev"
@@ -439,6 +490,15 @@ def decode_step(model, token: torch.Tensor, caches: list,
                 model.rope_cos, model.rope_sin, pos, cfg.num_heads)
             o = ops.paged_decode_attention(q, cache.kpool, cache.vpool,
                                            cache.block_table, pos)
+        elif fp8kv:
+            q = ops.decode_rope_cache_fp8kv(
+                qkv, cache.k8, cache.v8, cache.ks, cache.vs, model.rope_cos,
+                model.rope_sin, pos, cfg.num_heads)
+            if pos_dev is None:
+                cache.length = pos + 1
+            o = ops.decode_attention_fp8kv(
+                q, cache.k8, cache.v8, cache.ks, cache.vs,
+                pos + 1 if pos_dev is None else pos_dev)
         else:
             q = ops.decode_rope_cache(qkv, cache.k, cache.v, model.rope_cos,
                                       model.rope_sin, pos, cfg.num_heads)
@@ -466,9 +526,11 @@ def generate(
     temperature: float = 0.0,
     top_k: Optional[int] = None,
     max_len: Optional[int] = None,
+    kv_cache: str = "bf16",
 ) -> torch.Tensor:
     """Greedy (temperature=0) or top-k sampled continuation, for a Llama
-    or a Mixtral model. tokens [B, S0] -> [B, S0 + max_new_tokens]."""
+    or a Mixtral model. tokens [B, S0] -> [B, S0 + max_new_tokens].
+    ``kv_cache="fp8"`` keeps the KV cache in fp8 (``Fp8KVCache``)."""
     cfg = model.cfg
     B, S0 = tokens.shape
     total = S0 + max_new_tokens
@@ -476,8 +538,7 @@ def generate(
     assert total <= cfg.max_seq_len, (total, cfg.max_seq_len)
     assert max_len >= total
     device = tokens.device
-    caches = [KVCache.empty(cfg, B, max_len, device)
-              for _ in range(cfg.num_layers)]
+    caches = _dense_caches(kv_cache, cfg, B, max_len, device)
 
     def pick(logits: torch.Tensor) -> torch.Tensor:
         if temperature <= 0:
@@ -548,16 +609,17 @@ class GraphedDecoder:
 @torch.no_grad()
 def generate_graphed(model: LlamaModel, tokens: torch.Tensor,
                      max_new_tokens: int,
-                     max_len: Optional[int] = None) -> torch.Tensor:
-    """Greedy generation with the hipGraph decode loop (GPU only)."""
+                     max_len: Optional[int] = None,
+                     kv_cache: str = "bf16") -> torch.Tensor:
+    """Greedy generation with the hipGraph decode loop (GPU only);
+    ``kv_cache`` as in ``generate``."""
     cfg = model.cfg
     B, S0 = tokens.shape
     total = S0 + max_new_tokens
     max_len = max_len or total
     assert total <= cfg.max_seq_len and max_len >= total
     dev = tokens.device
-    caches = [KVCache.empty(cfg, B, max_len, dev)
-              for _ in range(cfg.num_layers)]
+    caches = _dense_caches(kv_cache, cfg, B, max_len, dev)
     out = [tokens]
     nxt = prefill(model, tokens, caches).argmax(-1, keepdim=True)
     out.append(nxt)
@@ -611,15 +673,15 @@ class ContinuousBatcher(_Batcher):
     Greedy decoding; rows are independent — admit() prefills ONE row's
     cache slice, step() advances every active row one token. The model
     may be a Llama or a Mixtral; ``prefill_fn`` / ``decode_fn`` are hooks
-    that replace ``prefill`` / ``decode_step``.
+    that replace ``prefill`` / ``decode_step``. ``kv_cache="fp8"`` keeps
+    the pool in fp8 (``Fp8KVCache``).
     """
 
     def __init__(self, model, max_batch: int, max_len: int,
-                 prefill_fn=None, decode_fn=None):
+                 prefill_fn=None, decode_fn=None, kv_cache: str = "bf16"):
         super().__init__(model, max_batch, max_len, prefill_fn, decode_fn)
-        self.caches = [KVCache.empty(self.cfg, max_batch, max_len,
-                                     self.device)
-                       for _ in range(self.cfg.num_layers)]
+        self.caches = _dense_caches(kv_cache, self.cfg, max_batch, max_len,
+                                    self.device)
 
     @torch.no_grad()
     def admit(self, row: int, prompt: torch.Tensor) -> torch.Tensor:
@@ -630,6 +692,7 @@ class ContinuousBatcher(_Batcher):
         S0 = prompt.numel()
         assert S0 + 1 < self.max_len
         row_caches = [
+            c.for_row(row) if isinstance(c, Fp8KVCache) else
             KVCache(k=c.k[row:row + 1], v=c.v[row:row + 1], length=0)
             for c in self.caches
         ]
@@ -718,7 +781,11 @@ class PagedBatcher(_Batcher):
                  page_size: int = 16, prefill_fn=None, decode_fn=None,
                  prefix_sharing: bool = False,
                  prefill_chunk: Optional[int] = None, extend_fn=None,
-                 ragged_fn=None):
+                 ragged_fn=None, kv_cache: str = "bf16"):
+        assert kv_cache == "bf16", \
+            "PagedBatcher keeps bf16 pools: the paged prefill kernels read " \
+            "bf16 pages, so an fp8 KV cache is served by the dense path " \
+            "only (generate, generate_graphed, ContinuousBatcher)"
         super().__init__(model, max_batch, max_len, prefill_fn, decode_fn)
         self._extend = extend_fn or prefill_extend
         self._ragged = ragged_fn or prefill_ragged

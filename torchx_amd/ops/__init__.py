@@ -794,6 +794,117 @@ def decode_attention_dev(q: torch.Tensor, kcache: torch.Tensor,
 
 
 # ---------------------------------------------------------------------------
+# fp8 KV cache (dense decode): k8 / v8 [B, T, Hkv, 128] float8_e4m3fn with
+# one fp32 scale per (token, kv head) in ks / vs [B, T, Hkv]; the value stood
+# for is ``k8 * ks[..., None]`` — ops/csrc/decode_attn_fp8kv.hip.
+# ---------------------------------------------------------------------------
+
+
+def quantize_kv_rows(x: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The KV-cache quantisation, by definition: per row of the last
+    dimension, ``scale = amax |x| / 448`` (1 for a zero row) and
+    ``x8 = e4m3(clamp(f32(x) / scale, -448, 448))``, both divisions in
+    fp32 and the cast round-to-nearest-even. x [..., D] -> (x8 [..., D]
+    float8_e4m3fn, scale [...] fp32). The HIP quantisers equal this bit
+    for bit; it is also the CPU path. The clamp precedes the cast as in
+    ``quantize_fp8_rows``. 448 is a tensor operand: torch turns a division
+    by a Python scalar on the GPU into a multiplication by its reciprocal,
+    which is not the IEEE quotient."""
+    xf = x.detach().float()
+    amax = xf.abs().amax(dim=-1)
+    scale = torch.where(amax > 0,
+                        amax / torch.full_like(amax, FP8_E4M3_MAX),
+                        torch.ones_like(amax))
+    y = (xf / scale[..., None]).clamp_(-FP8_E4M3_MAX, FP8_E4M3_MAX)
+    return y.to(torch.float8_e4m3fn), scale
+
+
+def dequantize_kv(x8: torch.Tensor, scale: torch.Tensor,
+                  dtype=torch.float32) -> torch.Tensor:
+    """``x8 * scale[..., None]`` in ``dtype``."""
+    return x8.to(dtype) * scale[..., None].to(dtype)
+
+
+def kv_quantize_store(k: torch.Tensor, v: torch.Tensor, k8: torch.Tensor,
+                      v8: torch.Tensor, ks: torch.Tensor, vs: torch.Tensor,
+                      start: int) -> None:
+    """Quantise k, v [B, S, Hkv, 128] bf16 (k already roped) into rows
+    ``start .. start+S-1`` of the fp8 cache, K and V in one launch."""
+    S = k.shape[1]
+    assert 0 <= start and start + S <= k8.shape[1], "rows outside the cache"
+    if _on_gpu(k, k8):
+        hip_ops().kv_quantize_store(k.contiguous(), v.contiguous(), k8, v8,
+                                    ks, vs, int(start))
+        return
+    k8[:, start:start + S], ks[:, start:start + S] = quantize_kv_rows(k)
+    v8[:, start:start + S], vs[:, start:start + S] = quantize_kv_rows(v)
+
+
+def decode_rope_cache_fp8kv(qkv: torch.Tensor, k8: torch.Tensor,
+                            v8: torch.Tensor, ks: torch.Tensor,
+                            vs: torch.Tensor, cos: torch.Tensor,
+                            sin: torch.Tensor, pos,
+                            num_heads: int) -> torch.Tensor:
+    """``decode_rope_cache`` over an fp8 cache: same qkv / ``pos`` contract
+    and the same roped q; the roped, bf16-rounded k and the raw v are
+    quantised (``quantize_kv_rows``) into row ``pos`` with their scales."""
+    if _on_gpu(qkv):
+        if isinstance(pos, torch.Tensor):
+            return hip_ops().decode_rope_cache_fp8kv(
+                qkv.contiguous(), k8, v8, ks, vs, cos, sin, 0,
+                pos.contiguous())
+        return hip_ops().decode_rope_cache_fp8kv(
+            qkv.contiguous(), k8, v8, ks, vs, cos, sin, int(pos), None)
+    # CPU: the bf16 op into a one-row scratch cache per sequence position
+    B = qkv.shape[0]
+    Hkv, D = k8.shape[2], k8.shape[3]
+    kc = torch.zeros(B, 1, Hkv, D, dtype=qkv.dtype)
+    vc = torch.zeros_like(kc)
+    if isinstance(pos, torch.Tensor):
+        rows = [int(p) for p in pos.reshape(-1).tolist()]
+        rows = rows * B if len(rows) == 1 else rows
+    else:
+        rows = [int(pos)] * B
+    outs = []
+    for b, p in enumerate(rows):
+        outs.append(decode_rope_cache(qkv[b:b + 1], kc[b:b + 1], vc[b:b + 1],
+                                      cos[p:p + 1], sin[p:p + 1], 0,
+                                      num_heads))
+        k8[b, p], ks[b, p] = quantize_kv_rows(kc[b, 0])
+        v8[b, p], vs[b, p] = quantize_kv_rows(vc[b, 0])
+    return torch.cat(outs, dim=0)
+
+
+def decode_attention_fp8kv(q: torch.Tensor, k8: torch.Tensor,
+                           v8: torch.Tensor, ks: torch.Tensor,
+                           vs: torch.Tensor, length_or_pos,
+                           scale: Optional[float] = None,
+                           split: Optional[int] = None) -> torch.Tensor:
+    """Decode attention of q [B, Hq, 128] bf16 over an fp8 cache -> o
+    [B, Hq, 128]. ``length_or_pos`` is a host int (the number of valid
+    rows), or an int32 tensor of positions as in ``decode_attention_dev``
+    (a scalar, or [B] for ragged rows; sequence b attends ``pos[b] + 1``
+    rows). One block serves the q heads of a GQA group from one read of
+    each row; Hq / Hkv must be 1, 2, 4 or 8. ``split`` forces the number
+    of length slices (1 = single pass); by default the launcher picks it."""
+    if scale is None:
+        scale = 1.0 / math.sqrt(q.shape[-1])
+    dev_pos = isinstance(length_or_pos, torch.Tensor)
+    if _on_gpu(q):
+        return hip_ops().decode_attn_fp8kv(
+            q.contiguous(), k8, v8, ks, vs,
+            0 if dev_pos else int(length_or_pos),
+            length_or_pos.contiguous() if dev_pos else None, scale,
+            int(split or 0))
+    # the fp32 reference over the fp32 dequantised caches
+    kc = dequantize_kv(k8, ks)
+    vc = dequantize_kv(v8, vs)
+    if dev_pos:
+        return decode_attention_dev(q, kc, vc, length_or_pos, scale)
+    return reference.decode_attention(q, kc, vc, int(length_or_pos), scale)
+
+
+# ---------------------------------------------------------------------------
 # Paged KV cache (serving): block-table counterparts of decode_attention_dev
 # and decode_rope_cache — ops/csrc/paged_attn.hip. kpool/vpool are
 # [num_pages, P, Hkv, D]; block_table int32 [B, M] maps logical page j of

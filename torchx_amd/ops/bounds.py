@@ -159,6 +159,51 @@ def decode_ref_bound(q: torch.Tensor, kcache: torch.Tensor,
     return {"o": r["o"][:, 0], "o_bound": r["o_bound"][:, 0]}
 
 
+def decode_fp8kv_ref_bound(q: torch.Tensor, k8: torch.Tensor,
+                           v8: torch.Tensor, ks: torch.Tensor,
+                           vs: torch.Tensor, lengths: Sequence[int],
+                           scale: float) -> Dict[str, torch.Tensor]:
+    """Decode attention over an fp8 cache: q [B,Hq,D] bf16, k8/v8
+    [B,T,Hkv,D] e4m3, ks/vs [B,T,Hkv] fp32 -> fp64 ``o`` [B,Hq,D] and
+    ``o_bound``.  The reference is the fp64 decode reference on the
+    dequantised caches k' = k8 ks, v' = v8 vs (exact in fp64), so the
+    quantisation error does not enter, and
+
+      |o - o64|_id <= (u + 2^-23 + 2 (e32 + 2^-23) max_j sabs_ij)
+                      sum_j p_ij |v'_jd|,     sabs on k'.
+
+    Against ``decode_ref_bound`` the kernel has two more roundings per row.
+    The score is ks_j * fl(sum_d (q_id scale) k8_jd): the fp32 dot product
+    is covered by e32 relative to sabs_ij as before (ks_j > 0 factors out of
+    both), and the multiply by ks_j adds one fp32 rounding, 2^-24 relative
+    to |s_ij| <= sabs_ij.  The PV term is (p_ij vs_j) * v8_jd: the product
+    p_ij vs_j is one more fp32 rounding, 2^-24 relative to p_ij |v'_jd|.
+    Each is doubled to 2^-23, as e32 is: an error of p enters o through the
+    numerator and through the normaliser.  P stays fp32, so the rounding
+    term is u, the output's."""
+    B, Hq, _ = q.shape
+    Hkv = k8.shape[2]
+    G = Hq // Hkv
+    lengths = [int(n) for n in lengths]
+    L = max(lengths)
+    kd = k8[:, :L].double() * ks[:, :L, :, None].double()
+    vd = v8[:, :L].double() * vs[:, :L, :, None].double()
+    qf = q.double()[:, :, None]                               # [B,Hq,1,D]
+    kf = _bhsd(kd).repeat_interleave(G, dim=1)                # [B,Hq,L,D]
+    vf = _bhsd(vd).repeat_interleave(G, dim=1)
+    vis = (torch.arange(L, device=q.device)[None, :] <
+           torch.tensor(lengths, device=q.device)[:, None])[:, None, None]
+    s = (qf @ kf.transpose(-1, -2)) * scale                   # [B,Hq,1,L]
+    s = s.masked_fill(~vis, float("-inf"))
+    sabs = (qf.abs() @ kf.abs().transpose(-1, -2)) * scale
+    sabs_max = sabs.masked_fill(~vis, 0.0).amax(-1)           # [B,Hq,1]
+    p = torch.softmax(s, dim=-1)
+    r23 = 2.0 ** -23
+    o_bound = (U + r23 + 2 * (E32 + r23) * sabs_max)[..., None] * (
+        p @ vf.abs())
+    return {"o": (p @ vf)[:, :, 0], "o_bound": o_bound[:, :, 0]}
+
+
 # ---------------------------------------------------------------------------
 # backward: reference + bound
 # ---------------------------------------------------------------------------

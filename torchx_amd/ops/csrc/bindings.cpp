@@ -101,6 +101,16 @@ void moe_gemv_down_combine_fp8w_launch(const void*, const void*, const void*,
                                        const void* const*, const void* const*,
                                        void*, int, int, int, int, int, int,
                                        hipStream_t);
+void kv_quantize_store_launch(const void*, const void*, void*, void*, void*,
+                              void*, int, int, int, int, int, hipStream_t);
+void decode_rope_cache_fp8kv_launch(const void*, void*, void*, void*, void*,
+                                    void*, const void*, const void*,
+                                    const void*, int, int, int, int, int, int,
+                                    int, hipStream_t);
+void decode_attn_fp8kv_launch(const void*, const void*, const void*,
+                              const void*, const void*, void*, void*, void*,
+                              const void*, int, int, int, int, int, int, int,
+                              float, int, hipStream_t);
 }
 
 namespace {
@@ -576,6 +586,160 @@ at::Tensor decode_attn_dev(at::Tensor q, at::Tensor kc, at::Tensor vc,
                        o.data_ptr(), pos.data_ptr(), B, Hq, Hkv, T, 0,
                        per_row, (float)scale, cur_stream());
   }
+  return o;
+}
+
+// ---- fp8 KV cache (decode_attn_fp8kv.hip) ----------------------------------
+// k8 / v8 [B, T, Hkv, 128] float8_e4m3fn, ks / vs [B, T, Hkv] fp32; the
+// value stood for is k8 * ks.
+namespace {
+
+struct Fp8kvDims {
+  int B, T, Hkv;
+};
+
+Fp8kvDims check_fp8kv_cache(const at::Tensor& k8, const at::Tensor& v8,
+                            const at::Tensor& ks, const at::Tensor& vs,
+                            const char* op) {
+  for (const at::Tensor* t : {&k8, &v8}) {
+    TORCH_CHECK(t->is_cuda() && t->scalar_type() == at::kFloat8_e4m3fn &&
+                    t->is_contiguous() && t->dim() == 4,
+                op, ": k8 / v8 must be contiguous float8_e4m3fn "
+                    "[B, T, Hkv, 128] device tensors");
+  }
+  TORCH_CHECK(k8.size(3) == 128, op, ": head_dim must be 128");
+  TORCH_CHECK(v8.sizes() == k8.sizes(), op, ": k8 / v8 shape mismatch");
+  TORCH_CHECK(k8.size(1) >= 1, op, ": empty cache");
+  for (const at::Tensor* t : {&ks, &vs}) {
+    check_f32(*t, "ks / vs");
+    TORCH_CHECK(t->dim() == 3 && t->size(0) == k8.size(0) &&
+                    t->size(1) == k8.size(1) && t->size(2) == k8.size(2),
+                op, ": ks / vs must be [B, T, Hkv]");
+  }
+  return {(int)k8.size(0), (int)k8.size(1), (int)k8.size(2)};
+}
+
+}  // namespace
+
+// k, v [B, S, Hkv, 128] bf16 (k already roped) -> rows start .. start+S-1
+// of the four cache tensors, quantised per (row, kv head).
+void kv_quantize_store(at::Tensor k, at::Tensor v, at::Tensor k8,
+                       at::Tensor v8, at::Tensor ks, at::Tensor vs,
+                       long start) {
+  check_bf16(k, "k");
+  check_bf16(v, "v");
+  const Fp8kvDims c = check_fp8kv_cache(k8, v8, ks, vs, "kv_quantize_store");
+  TORCH_CHECK(k.dim() == 4 && k.sizes() == v.sizes() && k.size(0) == c.B &&
+                  k.size(2) == c.Hkv && k.size(3) == 128,
+              "kv_quantize_store: k / v must be [B, S, Hkv, 128]");
+  const long S = k.size(1);
+  TORCH_CHECK(S >= 1 && start >= 0 && start + S <= c.T,
+              "kv_quantize_store: rows start .. start+S-1 outside the cache");
+  kv_quantize_store_launch(k.data_ptr(), v.data_ptr(), k8.data_ptr(),
+                           v8.data_ptr(), ks.data_ptr(), vs.data_ptr(), c.B,
+                           (int)S, c.Hkv, c.T, (int)start, cur_stream());
+}
+
+// decode_rope_cache over an fp8 cache: same qkv / pos contract, the roped k
+// and the raw v are quantised into row `pos` with their scales.
+at::Tensor decode_rope_cache_fp8kv(at::Tensor qkv, at::Tensor k8,
+                                   at::Tensor v8, at::Tensor ks,
+                                   at::Tensor vs, at::Tensor cos_t,
+                                   at::Tensor sin_t, long pos,
+                                   c10::optional<at::Tensor> pos_dev) {
+  check_bf16(qkv, "qkv");
+  check_f32(cos_t, "cos");
+  check_f32(sin_t, "sin");
+  const Fp8kvDims c =
+      check_fp8kv_cache(k8, v8, ks, vs, "decode_rope_cache_fp8kv");
+  const int B = qkv.size(0);
+  TORCH_CHECK(qkv.dim() == 2 && B == c.B, "qkv must be [B, (Hq+2*Hkv)*128]");
+  TORCH_CHECK(cos_t.dim() == 2 && cos_t.size(1) == 64 &&
+                  sin_t.sizes() == cos_t.sizes() && cos_t.size(0) >= 1,
+              "head_dim must be 128");
+  const long nh = qkv.size(1) / 128;
+  const int Hq = (int)nh - 2 * c.Hkv;
+  TORCH_CHECK(Hq >= 1 && qkv.size(1) == nh * 128, "qkv width mismatch");
+  const void* pd = nullptr;
+  int per_row = 0;
+  if (pos_dev.has_value()) {
+    TORCH_CHECK(pos_dev->is_cuda() && pos_dev->scalar_type() == at::kInt &&
+                    (pos_dev->numel() == 1 || pos_dev->numel() == B),
+                "pos_dev must be an int32 scalar or [B] device tensor");
+    TORCH_CHECK(pos_dev->is_contiguous(), "pos_dev must be contiguous");
+    pd = pos_dev->data_ptr();
+    per_row = pos_dev->numel() == B && B > 1 ? 1 : 0;
+  } else {
+    TORCH_CHECK(pos >= 0 && pos < c.T, "pos out of cache range");
+    TORCH_CHECK(pos < cos_t.size(0), "pos beyond rope table");
+  }
+  auto q = at::empty({B, (long)Hq, 128}, qkv.options());
+  decode_rope_cache_fp8kv_launch(
+      qkv.data_ptr(), q.data_ptr(), k8.data_ptr(), v8.data_ptr(),
+      ks.data_ptr(), vs.data_ptr(), cos_t.data_ptr(), sin_t.data_ptr(), pd, B,
+      Hq, c.Hkv, c.T, (int)cos_t.size(0), (int)pos, per_row, cur_stream());
+  return q;
+}
+
+// Split count of decode_attn_fp8kv for `blocks` = B * Hkv * head groups:
+// enough slices for 512 blocks (2 per CU), at most 32, and none shorter
+// than 128 rows (one unmasked U-group) of the T cache rows. It depends on
+// shapes only, never on the length, so the host-length and device-length
+// forms launch the same grid.
+static int fp8kv_split(long blocks, long T) {
+  const long want = (512 + blocks - 1) / blocks;
+  return (int)std::max(1L, std::min({want, 32L, T / 128}));
+}
+
+// q [B, Hq, 128] bf16 against the fp8 cache -> o [B, Hq, 128]. The length
+// is L (host) or pos_dev + 1 (int32 device scalar, or [B]). split = 0
+// takes the policy above; 1 forces the single pass, 2..32 that many slices.
+// kdot2 (the default, what the ops run) takes the QK product in the dot2
+// convert form; false is the fp32 form, kept for the measurement.
+at::Tensor decode_attn_fp8kv(at::Tensor q, at::Tensor k8, at::Tensor v8,
+                             at::Tensor ks, at::Tensor vs, long L,
+                             c10::optional<at::Tensor> pos_dev, double scale,
+                             long split, bool kdot2) {
+  check_bf16(q, "q");
+  const Fp8kvDims c = check_fp8kv_cache(k8, v8, ks, vs, "decode_attn_fp8kv");
+  TORCH_CHECK(q.dim() == 3 && q.size(0) == c.B && q.size(2) == 128,
+              "q must be [B, Hq, 128]");
+  const int B = c.B, Hq = q.size(1);
+  TORCH_CHECK(Hq % c.Hkv == 0, "GQA group mismatch");
+  const int G = Hq / c.Hkv;
+  TORCH_CHECK(G == 1 || G == 2 || G == 4 || G == 8,
+              "decode_attn_fp8kv: Hq / Hkv = ", G,
+              " has no kernel instance (1, 2, 4 and 8 do)");
+  const void* pd = nullptr;
+  int per_row = 0;
+  if (pos_dev.has_value()) {
+    TORCH_CHECK(pos_dev->is_cuda() && pos_dev->scalar_type() == at::kInt &&
+                    (pos_dev->numel() == 1 || pos_dev->numel() == B),
+                "pos must be an int32 scalar or [B] device tensor");
+    TORCH_CHECK(pos_dev->is_contiguous(), "pos must be contiguous");
+    pd = pos_dev->data_ptr();
+    per_row = pos_dev->numel() == B && B > 1 ? 1 : 0;
+  } else {
+    TORCH_CHECK(L >= 1 && L <= c.T, "invalid cache length");
+  }
+  TORCH_CHECK(split >= 0 && split <= 32, "split must be 0 (auto) .. 32");
+  const int NG = G == 8 ? 2 : 1;
+  const int sp = split ? (int)split
+                       : fp8kv_split((long)B * c.Hkv * NG, c.T);
+  auto o = at::empty_like(q);
+  at::Tensor ml, oacc;
+  void *mlp = nullptr, *oaccp = nullptr;
+  if (sp > 1) {
+    const long BHq = (long)B * Hq;
+    ml = at::empty({BHq * sp * 2}, q.options().dtype(at::kFloat));
+    oacc = at::empty({BHq * sp * 128}, q.options().dtype(at::kFloat));
+    mlp = ml.data_ptr();
+    oaccp = oacc.data_ptr();
+  }
+  decode_attn_fp8kv_launch(q.data_ptr(), k8.data_ptr(), v8.data_ptr(),
+                           ks.data_ptr(), vs.data_ptr(), o.data_ptr(), mlp,
+                           oaccp, pd, B, Hq, c.Hkv, c.T, (int)L, sp, per_row,
+                           (float)scale, kdot2 ? 1 : 0, cur_stream());
   return o;
 }
 
@@ -1209,6 +1373,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("qkv"), py::arg("kc"), py::arg("vc"), py::arg("cos"),
         py::arg("sin"), py::arg("pos") = 0,
         py::arg("pos_dev") = c10::nullopt);
+  m.def("kv_quantize_store", &kv_quantize_store);
+  m.def("decode_rope_cache_fp8kv", &decode_rope_cache_fp8kv,
+        py::arg("qkv"), py::arg("k8"), py::arg("v8"), py::arg("ks"),
+        py::arg("vs"), py::arg("cos"), py::arg("sin"), py::arg("pos") = 0,
+        py::arg("pos_dev") = c10::nullopt);
+  m.def("decode_attn_fp8kv", &decode_attn_fp8kv, py::arg("q"), py::arg("k8"),
+        py::arg("v8"), py::arg("ks"), py::arg("vs"), py::arg("L") = 0,
+        py::arg("pos_dev") = c10::nullopt, py::arg("scale") = 1.0,
+        py::arg("split") = 0, py::arg("kdot2") = true);
   m.def("paged_decode_attn", &paged_decode_attn);
   m.def("paged_decode_rope_cache", &paged_decode_rope_cache);
   m.def("paged_prefill_attn", &paged_prefill_attn);
