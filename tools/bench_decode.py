@@ -29,7 +29,8 @@ def run_batcher(args, model, tokens):
     def batcher():
         return PagedBatcher(model, B, max_len, B * -(-max_len // P) + 1, P,
                             prefix_sharing=shared is not None,
-                            prefill_chunk=args.prefill_chunk)
+                            prefill_chunk=args.prefill_chunk,
+                            kv_cache=args.kv_cache)
 
     # warm every prefill shape (hipBLASLt algo selection) on a batcher
     # that is thrown away, then time on a fresh one
@@ -70,7 +71,8 @@ def run_batcher(args, model, tokens):
         "batch": B, "prompt": S0, "new_tokens": N,
         "model": args.model, "dtype": "bf16", "weights": args.weights,
         "data": "synthetic",
-        "kv_cache": "paged", "page_size": P, "batcher": True,
+        "kv_cache": "paged", "kv_dtype": args.kv_cache, "page_size": P,
+        "batcher": True,
         "prefill_chunk": args.prefill_chunk, "shared_prefix": shared,
     }))
     return 0
@@ -103,7 +105,8 @@ def run_admit_many(args, model, tokens, rounds=5):
     def batcher():
         return PagedBatcher(model, B, max_len, B * -(-max_len // P) + 1, P,
                             prefix_sharing=shared is not None,
-                            prefill_chunk=args.prefill_chunk)
+                            prefill_chunk=args.prefill_chunk,
+                            kv_cache=args.kv_cache)
 
     def timed(fn):
         start = torch.cuda.Event(enable_timing=True)
@@ -173,7 +176,8 @@ def run_admit_many(args, model, tokens, rounds=5):
         "batch": B, "prompt": S0, "new_tokens": N,
         "model": args.model, "dtype": "bf16", "weights": args.weights,
         "data": "synthetic",
-        "kv_cache": "paged", "page_size": P, "batcher": True,
+        "kv_cache": "paged", "kv_dtype": args.kv_cache, "page_size": P,
+        "batcher": True,
         "admit_many": True,
         "prefill_chunk": args.prefill_chunk, "shared_prefix": shared,
     }))
@@ -222,12 +226,17 @@ def main():
                         "rows with an fp32 scale each (W8A16 GEMV kernels; "
                         "prefill stays bf16)")
     p.add_argument("--kv-cache", choices=["bf16", "fp8"], default="bf16",
-                   help="dense KV cache: bf16, or fp8 e4m3 rows with an fp32 "
-                        "scale per (token, kv head) (decode_attn_fp8kv.hip; "
-                        "not with --paged)")
+                   help="KV cache or page pools: bf16, or fp8 e4m3 rows with "
+                        "an fp32 scale per (token, kv head) "
+                        "(decode_attn_fp8kv.hip, paged_attn_fp8kv.hip; with "
+                        "--paged not with --prefill-chunk, --shared-prefix "
+                        "or --admit-many)")
     args = p.parse_args()
-    if args.kv_cache == "fp8" and args.paged:
-        print("--kv-cache fp8 is dense-only (the paged pools are bf16)",
+    if args.kv_cache == "fp8" and (args.prefill_chunk is not None
+                                   or args.shared_prefix is not None
+                                   or args.admit_many):
+        print("--kv-cache fp8 has no --prefill-chunk, --shared-prefix or "
+              "--admit-many: the paged prefill kernels read bf16 pages",
               file=sys.stderr)
         return 1
     if args.moe_decode is not None:
@@ -248,7 +257,8 @@ def main():
 
     from torchx_amd import ops
     from torchx_amd.models.generate import (
-        Fp8KVCache, KVCache, PagedKVCache, decode_step, prefill,
+        Fp8KVCache, Fp8PagedKVCache, KVCache, PagedKVCache, decode_step,
+        prefill,
     )
     from torchx_amd.models.llama import LlamaModel, llama3_8b, llama_gpu_tiny
 
@@ -289,14 +299,18 @@ def main():
         g = torch.Generator().manual_seed(0)
         table = (torch.randperm(B * M, generator=g) + 1).to(torch.int32)
         table = table.reshape(B, M).to(dev)
-        caches = [PagedKVCache.empty(cfg, B * M + 1, P, table, dev)
+        kind = Fp8PagedKVCache if args.kv_cache == "fp8" else PagedKVCache
+        caches = [kind.empty(cfg, B * M + 1, P, table, dev)
                   for _ in range(cfg.num_layers)]
         pos = torch.full((B,), S0, dtype=torch.int32, device=dev)
+        rows = [S0 + 1]  # host mirror of pos + 1, as PagedBatcher keeps
         dense_step = decode_step
 
         def decode_step(model, tok, caches):  # noqa: F811
-            logits = dense_step(model, tok, caches, pos_dev=pos)
+            hint = {"rows_hint": rows[0]} if args.kv_cache == "fp8" else {}
+            logits = dense_step(model, tok, caches, pos_dev=pos, **hint)
             pos.add_(1)
+            rows[0] += 1
             return logits
     else:
         kind = Fp8KVCache if args.kv_cache == "fp8" else KVCache

@@ -222,6 +222,60 @@ class PagedKVCache:
         return self.block_table[r0:r0 + batch]
 
 
+@dataclass
+class Fp8PagedKVCache:
+    """One layer's paged KV pool in fp8: ``PagedKVCache``'s pages, page 0
+    the dump page, holding ``Fp8KVCache``'s rows (e4m3 bytes plus one fp32
+    scale per (token, kv head)), 4 KB + 64 B per Llama-3-8B token row.
+    Filled by ``ops.paged_kv_quantize_store`` (prefill) and
+    ``ops.paged_decode_rope_cache_fp8kv`` (decode), read by
+    ``ops.paged_decode_attention_fp8kv``. The pools start as zeros with zero
+    scales: a retired row attends row 0 of page 0, which nothing but other
+    retired rows ever writes, and a zero row stays finite."""
+    k8pool: torch.Tensor  # [num_pages, P, Hkv, 128] float8_e4m3fn
+    v8pool: torch.Tensor
+    kspool: torch.Tensor  # [num_pages, P, Hkv] fp32
+    vspool: torch.Tensor
+    block_table: torch.Tensor
+    row: Optional[int] = None
+
+    @staticmethod
+    def empty(cfg: LlamaConfig, num_pages: int, page_size: int,
+              block_table: torch.Tensor,
+              device: torch.device) -> "Fp8PagedKVCache":
+        assert 16 <= page_size <= 256 and page_size & (page_size - 1) == 0
+        shape = (num_pages, page_size, cfg.num_kv_heads, cfg.head_dim)
+        return Fp8PagedKVCache(
+            k8pool=torch.zeros(shape, dtype=torch.float8_e4m3fn,
+                               device=device),
+            v8pool=torch.zeros(shape, dtype=torch.float8_e4m3fn,
+                               device=device),
+            kspool=torch.zeros(shape[:3], dtype=torch.float32, device=device),
+            vspool=torch.zeros(shape[:3], dtype=torch.float32, device=device),
+            block_table=block_table,
+        )
+
+    @property
+    def page_size(self) -> int:
+        return self.k8pool.shape[1]
+
+    @property
+    def pools(self) -> tuple:
+        return self.k8pool, self.v8pool, self.kspool, self.vspool
+
+    def for_row(self, row: int) -> "Fp8PagedKVCache":
+        return Fp8PagedKVCache(*self.pools, self.block_table, row)
+
+    def store_prefix(self, k: torch.Tensor, v: torch.Tensor) -> None:
+        """Quantise a prefilled prefix into the pages of its row(s), rows
+        chosen as ``PagedKVCache.store_prefix`` chooses them: one kernel,
+        no host sync."""
+        ops.paged_kv_quantize_store(k, v, *self.pools,
+                                    self.table_rows(k.shape[0]), 0)
+
+    table_rows = PagedKVCache.table_rows
+
+
 def _split_qkv(qkv: torch.Tensor, cfg: LlamaConfig):
     B, S, _ = qkv.shape
     q, k, v = qkv.split([cfg.q_dim, cfg.kv_dim, cfg.kv_dim], dim=-1)
@@ -316,12 +370,12 @@ def _prefill_pass(model, tokens: torch.Tensor, caches: list, start: int,
 def prefill(model, tokens: torch.Tensor, caches: list) -> torch.Tensor:
     """Run the prompt through the model (Llama or Mixtral), filling
     per-layer KV caches of any kind; attention is the dense training
-    kernel on the fresh bf16 k/v (an ``Fp8KVCache`` only stores their
-    quantised rows). Returns the last position's logits [B, vocab]."""
+    kernel on the fresh bf16 k/v (an ``Fp8KVCache`` or ``Fp8PagedKVCache``
+    only stores their quantised rows). Returns the last position's logits [B, vocab]."""
     S = tokens.shape[1]
 
     def attend(cache, q, k, v):
-        if isinstance(cache, PagedKVCache):
+        if isinstance(cache, (PagedKVCache, Fp8PagedKVCache)):
             cache.store_prefix(k, v)
         elif isinstance(cache, Fp8KVCache):
             ops.kv_quantize_store(k, v, cache.k8, cache.v8, cache.ks,
@@ -453,7 +507,8 @@ def prefill_ragged(model, tokens: torch.Tensor, caches: list,
 
 @torch.no_grad()
 def decode_step(model, token: torch.Tensor, caches: list,
-                pos_dev: Optional[torch.Tensor] = None) -> torch.Tensor:
+                pos_dev: Optional[torch.Tensor] = None,
+                rows_hint: Optional[int] = None) -> torch.Tensor:
     """One token [B, 1] -> next-position logits [B, vocab], appending to
     the caches. Fully fused decode layer (8 dispatches on GPU): skinny-M
     GEMV x3 + fused GEMV-SwiGLU x1, rope+cache-append x1, split-K
@@ -468,13 +523,16 @@ def decode_step(model, token: torch.Tensor, caches: list,
     position-independent; its routing reads the device, so only the
     dense model's step is capturable. ``Fp8KVCache`` caches take all three
     ``pos`` forms through the fp8 KV kernels (quantising append, GQA-shared
-    attention)."""
+    attention), ``Fp8PagedKVCache`` caches the [B] vector through their
+    block-table forms; ``rows_hint`` is a host bound on ``pos + 1`` that
+    sizes their attention split (``ops.paged_decode_attention_fp8kv``)."""
     cfg = model.cfg
     B = token.shape[0]
     blocks = model.blocks
     paged = isinstance(caches[0], PagedKVCache)
+    paged8 = isinstance(caches[0], Fp8PagedKVCache)
     fp8kv = isinstance(caches[0], Fp8KVCache)
-    if paged:
+    if paged or paged8:
         assert pos_dev is not None and pos_dev.numel() == B, \
             "paged caches need an int32 [B] pos_dev"
         pos = pos_dev
@@ -490,6 +548,12 @@ def decode_step(model, token: torch.Tensor, caches: list,
                 model.rope_cos, model.rope_sin, pos, cfg.num_heads)
             o = ops.paged_decode_attention(q, cache.kpool, cache.vpool,
                                            cache.block_table, pos)
+        elif paged8:
+            q = ops.paged_decode_rope_cache_fp8kv(
+                qkv, *cache.pools, cache.block_table, model.rope_cos,
+                model.rope_sin, pos, cfg.num_heads)
+            o = ops.paged_decode_attention_fp8kv(
+                q, *cache.pools, cache.block_table, pos, rows_hint=rows_hint)
         elif fp8kv:
             q = ops.decode_rope_cache_fp8kv(
                 qkv, cache.k8, cache.v8, cache.ks, cache.vs, model.rope_cos,
@@ -770,6 +834,13 @@ class PagedBatcher(_Batcher):
     together, packed, through ``prefill_ragged``; it honours both options
     above and leaves the same state as one ``admit`` per request.
 
+    ``kv_cache="fp8"`` keeps the pools in fp8 (``Fp8PagedKVCache``, half
+    the bytes per token row): ``admit`` (the whole-prompt path), ``step``,
+    ``retire`` and preemption work as for bf16, and ``step`` sizes the
+    attention split for the longest live row. ``prefix_sharing``,
+    ``prefill_chunk`` and ``admit_many`` are refused with fp8 pools: their
+    paged prefill kernels read bf16 pages.
+
     The model may be a Llama or a Mixtral: the passes tell them apart by
     the block. ``prefill_fn``, ``decode_fn``, ``extend_fn`` and
     ``ragged_fn`` are hooks that replace ``prefill``, ``decode_step``,
@@ -782,10 +853,12 @@ class PagedBatcher(_Batcher):
                  prefix_sharing: bool = False,
                  prefill_chunk: Optional[int] = None, extend_fn=None,
                  ragged_fn=None, kv_cache: str = "bf16"):
-        assert kv_cache == "bf16", \
-            "PagedBatcher keeps bf16 pools: the paged prefill kernels read " \
-            "bf16 pages, so an fp8 KV cache is served by the dense path " \
-            "only (generate, generate_graphed, ContinuousBatcher)"
+        assert kv_cache in KV_CACHE_KINDS, \
+            f"kv_cache must be one of {KV_CACHE_KINDS}, got {kv_cache!r}"
+        self.fp8kv = kv_cache == "fp8"
+        for name, on in (("prefix_sharing", prefix_sharing),
+                         ("prefill_chunk", prefill_chunk is not None)):
+            assert not (self.fp8kv and on), self._no_fp8_prefill(name)
         super().__init__(model, max_batch, max_len, prefill_fn, decode_fn)
         self._extend = extend_fn or prefill_extend
         self._ragged = ragged_fn or prefill_ragged
@@ -801,14 +874,21 @@ class PagedBatcher(_Batcher):
         self.table_width = -(-max_len // page_size)
         self.block_table = torch.zeros(max_batch, self.table_width,
                                        dtype=torch.int32, device=dev)
-        self.caches = [PagedKVCache.empty(self.cfg, num_pages, page_size,
-                                          self.block_table, dev)
+        kind = Fp8PagedKVCache if self.fp8kv else PagedKVCache
+        self.caches = [kind.empty(self.cfg, num_pages, page_size,
+                                  self.block_table, dev)
                        for _ in range(self.cfg.num_layers)]
         self.allocator = PageAllocator(num_pages)
         self.pages = [[] for _ in range(max_batch)]  # pages owned per row
         # 1 for active rows: only those advance (pos.add_(mask))
         self.mask = torch.zeros(max_batch, dtype=torch.int32, device=dev)
         self.preempted = []
+
+    @staticmethod
+    def _no_fp8_prefill(what: str) -> str:
+        return (f"{what} needs kv_cache='bf16': it runs prefill_extend / "
+                "prefill_ragged, whose MFMA paged prefill kernels read bf16 "
+                "pages; the fp8 prefill kernels over fp8 pages are missing")
 
     def free_pages(self) -> int:
         return self.allocator.num_free
@@ -942,6 +1022,7 @@ class PagedBatcher(_Batcher):
         pass: the prompts are packed greedily in call order and split
         across passes where needed, so every token of i is in the same
         or an earlier pass than any token of j > i."""
+        assert not self.fp8kv, self._no_fp8_prefill("admit_many")
         rows = [int(r) for r in rows]
         assert len(rows) == len(prompts) >= 1
         assert len(set(rows)) == len(rows), "rows must be distinct"
@@ -1035,8 +1116,12 @@ class PagedBatcher(_Batcher):
                     continue
                 self.block_table[i, len(self.pages[i])] = page
                 self.pages[i].append(page)
+        # fp8 pools: the attention split follows the longest live row, from
+        # the host mirror (a retired row attends one row)
+        hint = ({"rows_hint": max(p + 1 for p in self.pos_host)}
+                if self.fp8kv else {})
         logits = self._decode(self.model, self.tok, self.caches,
-                              pos_dev=self.pos)
+                              pos_dev=self.pos, **hint)
         nxt = logits.argmax(-1, keepdim=True)
         self.tok.copy_(nxt)
         self.pos.add_(self.mask)

@@ -1103,6 +1103,119 @@ def paged_decode_rope_cache(qkv: torch.Tensor, kpool: torch.Tensor,
     return torch.cat(outs, dim=0).reshape(B, num_heads, D)
 
 
+# ---------------------------------------------------------------------------
+# Paged fp8 KV cache: the block-table forms of the three fp8 KV ops —
+# ops/csrc/paged_attn_fp8kv.hip. k8pool / v8pool [num_pages, P, Hkv, 128]
+# float8_e4m3fn, kspool / vspool [num_pages, P, Hkv] fp32; block_table and
+# pos as for the bf16 pools. The CPU paths gather the logical cache and run
+# the dense fp8 ops' CPU paths.
+# ---------------------------------------------------------------------------
+
+
+def _paged_gather_fp8kv(k8pool, v8pool, kspool, vspool, table_row, n: int):
+    """The first ``n`` logical rows of one sequence as a dense fp8 cache
+    (k8, v8, ks, vs) of batch 1. The bytes are gathered as uint8."""
+    k8, v8 = (reference.paged_gather(p.view(torch.uint8), table_row, n)
+              .view(torch.float8_e4m3fn) for p in (k8pool, v8pool))
+    return (k8, v8, reference.paged_gather(kspool, table_row, n),
+            reference.paged_gather(vspool, table_row, n))
+
+
+def paged_decode_attention_fp8kv(q: torch.Tensor, k8pool: torch.Tensor,
+                                 v8pool: torch.Tensor, kspool: torch.Tensor,
+                                 vspool: torch.Tensor,
+                                 block_table: torch.Tensor, pos: torch.Tensor,
+                                 scale: Optional[float] = None,
+                                 split: Optional[int] = None,
+                                 rows_hint: Optional[int] = None
+                                 ) -> torch.Tensor:
+    """``decode_attention_fp8kv`` over paged fp8 pools: q [B, Hq, 128];
+    sequence b attends its ``pos[b] + 1`` logical rows, row t read from
+    ``pool[block_table[b, t // P], t % P]`` -> o [B, Hq, 128]. ``pos`` is
+    int32 [B]. On the GPU, for the same split count the result is
+    bit-identical to ``decode_attention_fp8kv`` on the same logical cache.
+    ``split`` forces the number of length slices (1 = single pass). By
+    default the launcher sizes it for ``rows_hint`` rows, a host bound on
+    the rows any sequence attends (``PagedBatcher`` passes its host mirror
+    of ``pos``); without a hint it assumes the table's capacity M * P."""
+    if scale is None:
+        scale = 1.0 / math.sqrt(q.shape[-1])
+    if _on_gpu(q):
+        return hip_ops().paged_decode_attn_fp8kv(
+            q.contiguous(), k8pool, v8pool, kspool, vspool, block_table,
+            pos.contiguous(), scale, int(split or 0), int(rows_hint or 0))
+    outs = []
+    for b in range(q.shape[0]):
+        n = int(pos[b].item()) + 1
+        outs.append(decode_attention_fp8kv(
+            q[b:b + 1], *_paged_gather_fp8kv(k8pool, v8pool, kspool, vspool,
+                                             block_table[b], n), n, scale))
+    return torch.cat(outs, dim=0)
+
+
+def paged_decode_rope_cache_fp8kv(qkv: torch.Tensor, k8pool: torch.Tensor,
+                                  v8pool: torch.Tensor, kspool: torch.Tensor,
+                                  vspool: torch.Tensor,
+                                  block_table: torch.Tensor,
+                                  cos: torch.Tensor, sin: torch.Tensor,
+                                  pos: torch.Tensor,
+                                  num_heads: int) -> torch.Tensor:
+    """``decode_rope_cache_fp8kv`` through the table: qkv
+    [B, (Hq+2*Hkv)*128] for one position -> roped q [B, Hq, 128]; the
+    roped, bf16-rounded k and the raw v of sequence b are quantised
+    (``quantize_kv_rows``) into pool slot
+    ``block_table[b, pos[b] // P] * P + pos[b] % P``. cos/sin are the FULL
+    f32 [S, 64] tables; ``pos`` is int32 [B]."""
+    if _on_gpu(qkv):
+        return hip_ops().paged_decode_rope_cache_fp8kv(
+            qkv.contiguous(), k8pool, v8pool, kspool, vspool, block_table,
+            cos, sin, pos.contiguous())
+    # CPU: the dense op into a one-row scratch cache, then the page slot
+    B = qkv.shape[0]
+    P, Hkv, D = k8pool.shape[1:]
+    k8 = torch.zeros(B, 1, Hkv, D, dtype=torch.float8_e4m3fn)
+    v8 = torch.zeros_like(k8)
+    ks = torch.ones(B, 1, Hkv)
+    vs = torch.ones(B, 1, Hkv)
+    outs = []
+    for b in range(B):
+        p = int(pos[b].item())
+        outs.append(decode_rope_cache_fp8kv(
+            qkv[b:b + 1], k8[b:b + 1], v8[b:b + 1], ks[b:b + 1], vs[b:b + 1],
+            cos[p:p + 1], sin[p:p + 1], 0, num_heads))
+        page = int(block_table[b, p // P].item())
+        k8pool[page, p % P], kspool[page, p % P] = k8[b, 0], ks[b, 0]
+        v8pool[page, p % P], vspool[page, p % P] = v8[b, 0], vs[b, 0]
+    return torch.cat(outs, dim=0)
+
+
+def paged_kv_quantize_store(k: torch.Tensor, v: torch.Tensor,
+                            k8pool: torch.Tensor, v8pool: torch.Tensor,
+                            kspool: torch.Tensor, vspool: torch.Tensor,
+                            table_rows: torch.Tensor, start: int) -> None:
+    """``kv_quantize_store`` into pages: k, v [B, S, Hkv, 128] bf16 (k
+    already roped) become the logical rows ``start .. start+S-1`` of the
+    sequences whose block-table rows are ``table_rows`` int32 [B, M], K and
+    V in one launch."""
+    B, S = k.shape[:2]
+    P = k8pool.shape[1]
+    assert table_rows.shape[0] == B, "one table row per sequence"
+    assert 0 <= start and start + S <= table_rows.shape[1] * P, \
+        "rows outside the table"
+    if _on_gpu(k, k8pool):
+        hip_ops().paged_kv_quantize_store(
+            k.contiguous(), v.contiguous(), k8pool, v8pool, kspool, vspool,
+            table_rows.contiguous(), int(start))
+        return
+    t = torch.arange(start, start + S)
+    for x, pool8, pools in ((k, k8pool, kspool), (v, v8pool, vspool)):
+        x8, xs = quantize_kv_rows(x)
+        for b in range(B):
+            pages = table_rows[b, t // P].long()
+            pool8.view(torch.uint8)[pages, t % P] = x8[b].view(torch.uint8)
+            pools[pages, t % P] = xs[b]
+
+
 def decode_linear(x: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
     """Skinny-M linear for the decode path: x [..., M, K] with M <= 8
     total rows -> x @ w.T via the W-stream-bound ``gemv_bf16`` kernel

@@ -27,6 +27,7 @@ SOURCES = [
     "decode_attn.hip",
     "decode_attn_fp8kv.hip",
     "paged_attn.hip",
+    "paged_attn_fp8kv.hip",
     "gemv.hip",
     "gemv_fp8.hip",
     "gemm_fp8w_mfma.hip",
@@ -47,6 +48,7 @@ EXTRA_FLAGS = {
     "gemv_fp8.hip": _NO_PK_F32,
     "gemm_fp8w_mfma.hip": _NO_PK_F32,
     "decode_attn_fp8kv.hip": _NO_PK_F32,
+    "paged_attn_fp8kv.hip": _NO_PK_F32,
 }
 
 

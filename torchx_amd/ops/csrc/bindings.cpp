@@ -111,6 +111,19 @@ void decode_attn_fp8kv_launch(const void*, const void*, const void*,
                               const void*, const void*, void*, void*, void*,
                               const void*, int, int, int, int, int, int, int,
                               float, int, hipStream_t);
+void paged_decode_attn_fp8kv_launch(const void*, const void*, const void*,
+                                    const void*, const void*, void*, void*,
+                                    void*, const void*, const void*, int, int,
+                                    int, int, int, int, int, float,
+                                    hipStream_t);
+void paged_decode_rope_cache_fp8kv_launch(const void*, void*, void*, void*,
+                                          void*, void*, const void*,
+                                          const void*, const void*,
+                                          const void*, int, int, int, int,
+                                          int, int, int, hipStream_t);
+void paged_kv_quantize_store_launch(const void*, const void*, void*, void*,
+                                    void*, void*, const void*, int, int, int,
+                                    int, int, int, int, hipStream_t);
 }
 
 namespace {
@@ -1151,6 +1164,156 @@ at::Tensor paged_decode_rope_cache(at::Tensor qkv, at::Tensor kpool,
   return q;
 }
 
+// ---- paged fp8 KV cache (paged_attn_fp8kv.hip) -----------------------------
+// k8pool / v8pool [num_pages, P, Hkv, 128] float8_e4m3fn, kspool / vspool
+// [num_pages, P, Hkv] fp32, block_table int32 [rows, M]. As for the bf16
+// pools the kernels clamp every table entry and position, so the checks are
+// about shapes and dtypes. Returns log2(P).
+namespace {
+
+int check_paged_fp8kv(const at::Tensor& k8pool, const at::Tensor& v8pool,
+                      const at::Tensor& kspool, const at::Tensor& vspool,
+                      const at::Tensor& bt, long B, const char* op) {
+  // the pools have the dense fp8 cache's layout with (num_pages, P) for
+  // (B, T)
+  check_fp8kv_cache(k8pool, v8pool, kspool, vspool, op);
+  const long P = k8pool.size(1);
+  TORCH_CHECK(P >= 16 && P <= 256 && (P & (P - 1)) == 0, op,
+              ": page size must be a power of two in [16, 256]");
+  TORCH_CHECK(k8pool.size(0) * P < (1L << 31), op, ": invalid num_pages");
+  TORCH_CHECK(bt.is_cuda() && bt.scalar_type() == at::kInt &&
+                  bt.dim() == 2 && bt.is_contiguous(),
+              op, ": block_table must be a contiguous int32 [B, M] device "
+                  "tensor");
+  TORCH_CHECK(bt.size(0) == B, op,
+              ": block_table rows must equal the batch");
+  TORCH_CHECK(bt.size(1) >= 1 && bt.size(1) * P < (1L << 31), op,
+              ": invalid block_table width");
+  int logP = 0;
+  while ((1L << logP) < P) ++logP;
+  return logP;
+}
+
+void check_paged_pos(const at::Tensor& pos, long B, const char* op) {
+  TORCH_CHECK(pos.is_cuda() && pos.scalar_type() == at::kInt &&
+                  pos.is_contiguous() && pos.numel() == B,
+              op, ": pos must be a contiguous int32 [B] device tensor");
+}
+
+}  // namespace
+
+// q [B, Hq, 128] bf16 over the fp8 pools through the table -> o [B, Hq,
+// 128]; row b attends pos[b] + 1 rows. split = 0 takes fp8kv_split with
+// rows_hint (a host bound on the rows any sequence attends; 0 = M * P, the
+// capacity) in place of the dense cache's T: a paged table is sized for the
+// longest sequence it may ever hold, which says little about the rows in
+// use. 1 forces the single pass, 2..32 that many slices.
+at::Tensor paged_decode_attn_fp8kv(at::Tensor q, at::Tensor k8pool,
+                                   at::Tensor v8pool, at::Tensor kspool,
+                                   at::Tensor vspool, at::Tensor bt,
+                                   at::Tensor pos, double scale, long split,
+                                   long rows_hint) {
+  const char* op = "paged_decode_attn_fp8kv";
+  check_bf16(q, "q");
+  TORCH_CHECK(q.dim() == 3 && q.size(2) == 128, "q must be [B, Hq, 128]");
+  const int B = q.size(0), Hq = q.size(1);
+  const int logP =
+      check_paged_fp8kv(k8pool, v8pool, kspool, vspool, bt, B, op);
+  check_paged_pos(pos, B, op);
+  const int num_pages = k8pool.size(0), Hkv = k8pool.size(2);
+  const int M = bt.size(1);
+  TORCH_CHECK(Hq % Hkv == 0, "GQA group mismatch");
+  const int G = Hq / Hkv;
+  TORCH_CHECK(G == 1 || G == 2 || G == 4 || G == 8, op, ": Hq / Hkv = ", G,
+              " has no kernel instance (1, 2, 4 and 8 do)");
+  TORCH_CHECK(split >= 0 && split <= 32, "split must be 0 (auto) .. 32");
+  TORCH_CHECK(rows_hint >= 0, "rows_hint must be >= 0 (0 = the capacity)");
+  const long cap = (long)M << logP;
+  const int NG = G == 8 ? 2 : 1;
+  const int sp =
+      split ? (int)split
+            : fp8kv_split((long)B * Hkv * NG,
+                          rows_hint ? std::min(rows_hint, cap) : cap);
+  auto o = at::empty_like(q);
+  at::Tensor ml, oacc;
+  void *mlp = nullptr, *oaccp = nullptr;
+  if (sp > 1) {
+    const long BHq = (long)B * Hq;
+    ml = at::empty({BHq * sp * 2}, q.options().dtype(at::kFloat));
+    oacc = at::empty({BHq * sp * 128}, q.options().dtype(at::kFloat));
+    mlp = ml.data_ptr();
+    oaccp = oacc.data_ptr();
+  }
+  paged_decode_attn_fp8kv_launch(
+      q.data_ptr(), k8pool.data_ptr(), v8pool.data_ptr(), kspool.data_ptr(),
+      vspool.data_ptr(), o.data_ptr(), mlp, oaccp, bt.data_ptr(),
+      pos.data_ptr(), B, Hq, Hkv, num_pages, logP, M, sp, (float)scale,
+      cur_stream());
+  return o;
+}
+
+// qkv [B, (Hq+2*Hkv)*128] (one position): ropes q/k at pos[b], quantises
+// k/v into pool slot bt[b][pos/P]*P + pos%P, returns q [B, Hq, 128].
+at::Tensor paged_decode_rope_cache_fp8kv(at::Tensor qkv, at::Tensor k8pool,
+                                         at::Tensor v8pool, at::Tensor kspool,
+                                         at::Tensor vspool, at::Tensor bt,
+                                         at::Tensor cos_t, at::Tensor sin_t,
+                                         at::Tensor pos) {
+  const char* op = "paged_decode_rope_cache_fp8kv";
+  check_bf16(qkv, "qkv");
+  check_f32(cos_t, "cos");
+  check_f32(sin_t, "sin");
+  TORCH_CHECK(qkv.dim() == 2, "qkv must be [B, (Hq+2*Hkv)*128]");
+  const int B = qkv.size(0);
+  const int logP =
+      check_paged_fp8kv(k8pool, v8pool, kspool, vspool, bt, B, op);
+  check_paged_pos(pos, B, op);
+  const int num_pages = k8pool.size(0), Hkv = k8pool.size(2);
+  const int M = bt.size(1);
+  TORCH_CHECK(cos_t.dim() == 2 && cos_t.size(1) == 64 &&
+                  cos_t.size(0) >= 1 && sin_t.sizes() == cos_t.sizes(),
+              "cos/sin must be [S, 64] (head_dim 128)");
+  const long nh = qkv.size(1) / 128;
+  const int Hq = (int)nh - 2 * Hkv;
+  TORCH_CHECK(Hq >= 1 && qkv.size(1) == nh * 128, "qkv width mismatch");
+  TORCH_CHECK(Hq % Hkv == 0, "GQA group mismatch");
+  const int rope_rows = (int)std::min<long>(cos_t.size(0), 1L << 30);
+  auto q = at::empty({B, (long)Hq, 128}, qkv.options());
+  paged_decode_rope_cache_fp8kv_launch(
+      qkv.data_ptr(), q.data_ptr(), k8pool.data_ptr(), v8pool.data_ptr(),
+      kspool.data_ptr(), vspool.data_ptr(), bt.data_ptr(), cos_t.data_ptr(),
+      sin_t.data_ptr(), pos.data_ptr(), B, Hq, Hkv, num_pages, logP, M,
+      rope_rows, cur_stream());
+  return q;
+}
+
+// k, v [B, S, Hkv, 128] bf16 (k already roped) -> logical rows start ..
+// start+S-1 of the sequences whose table rows are table_rows [B, M],
+// quantised per (row, kv head) into their pages.
+void paged_kv_quantize_store(at::Tensor k, at::Tensor v, at::Tensor k8pool,
+                             at::Tensor v8pool, at::Tensor kspool,
+                             at::Tensor vspool, at::Tensor table_rows,
+                             long start) {
+  const char* op = "paged_kv_quantize_store";
+  check_bf16(k, "k");
+  check_bf16(v, "v");
+  TORCH_CHECK(k.dim() == 4 && k.sizes() == v.sizes() && k.size(3) == 128, op,
+              ": k / v must be [B, S, Hkv, 128]");
+  const long B = k.size(0), S = k.size(1);
+  const int logP = check_paged_fp8kv(k8pool, v8pool, kspool, vspool,
+                                     table_rows, B, op);
+  const int num_pages = k8pool.size(0), Hkv = k8pool.size(2);
+  const int M = table_rows.size(1);
+  TORCH_CHECK(k.size(2) == Hkv, op, ": k / v must be [B, S, Hkv, 128]");
+  TORCH_CHECK(B >= 1 && S >= 1 && start >= 0 &&
+                  start + S <= ((long)M << logP),
+              op, ": rows start .. start+S-1 outside the table");
+  paged_kv_quantize_store_launch(
+      k.data_ptr(), v.data_ptr(), k8pool.data_ptr(), v8pool.data_ptr(),
+      kspool.data_ptr(), vspool.data_ptr(), table_rows.data_ptr(), (int)B,
+      (int)S, Hkv, num_pages, logP, M, (int)start, cur_stream());
+}
+
 // q [B, S, Hq, 128]: a chunk of S query rows at logical positions
 // ctx[b] .. ctx[b]+S-1, attending the ctx[b]+S rows the pools already hold
 // for sequence b (causal). Returns o [B, S, Hq, 128].
@@ -1384,6 +1547,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("split") = 0, py::arg("kdot2") = true);
   m.def("paged_decode_attn", &paged_decode_attn);
   m.def("paged_decode_rope_cache", &paged_decode_rope_cache);
+  m.def("paged_decode_attn_fp8kv", &paged_decode_attn_fp8kv, py::arg("q"),
+        py::arg("k8pool"), py::arg("v8pool"), py::arg("kspool"),
+        py::arg("vspool"), py::arg("block_table"), py::arg("pos"),
+        py::arg("scale") = 1.0, py::arg("split") = 0,
+        py::arg("rows_hint") = 0);
+  m.def("paged_decode_rope_cache_fp8kv", &paged_decode_rope_cache_fp8kv);
+  m.def("paged_kv_quantize_store", &paged_kv_quantize_store);
   m.def("paged_prefill_attn", &paged_prefill_attn);
   m.def("paged_prefill_attn_ragged", &paged_prefill_attn_ragged);
   m.def("paged_prefill_rope_cache", &paged_prefill_rope_cache);

@@ -58,6 +58,16 @@ struct PagedRows {
   }
 };
 
+// rows a paged sequence attends, for pos int32 [B] and a table [B, M]
+__device__ __forceinline__ int paged_len(const int* __restrict__ pos, int b,
+                                         int M, int logP) {
+  // L = pos + 1 clamped to [0, M*P]; compare before adding so a garbage
+  // pos cannot overflow
+  const int cap = M << logP;
+  const int p = pos[b];
+  return p < 0 ? 0 : (p >= cap ? cap : p + 1);
+}
+
 // ---- epilogues: what wave 0 does with the block's (m, l, o[128]) ----------
 
 // normalise and store the bf16 output row; `o` points at o[b, hq, 0]

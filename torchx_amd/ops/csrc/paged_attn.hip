@@ -15,15 +15,6 @@
 // is next to PagedRows.
 #include "decode_core.h"
 
-__device__ __forceinline__ int paged_len(const int* __restrict__ pos, int b,
-                                         int M, int logP) {
-  // L = pos + 1 clamped to [0, M*P]; compare before adding so a garbage
-  // pos cannot overflow
-  const int cap = M << logP;
-  const int p = pos[b];
-  return p < 0 ? 0 : (p >= cap ? cap : p + 1);
-}
-
 __device__ __forceinline__ PagedRows paged_rows(
     const unsigned short* __restrict__ kpool,
     const unsigned short* __restrict__ vpool, const int* __restrict__ bt_row,
