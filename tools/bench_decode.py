@@ -30,7 +30,8 @@ def run_batcher(args, model, tokens):
         return PagedBatcher(model, B, max_len, B * -(-max_len // P) + 1, P,
                             prefix_sharing=shared is not None,
                             prefill_chunk=args.prefill_chunk,
-                            kv_cache=args.kv_cache)
+                            kv_cache=args.kv_cache,
+                            fp8_prefill=args.fp8_prefill)
 
     # warm every prefill shape (hipBLASLt algo selection) on a batcher
     # that is thrown away, then time on a fresh one
@@ -106,7 +107,8 @@ def run_admit_many(args, model, tokens, rounds=5):
         return PagedBatcher(model, B, max_len, B * -(-max_len // P) + 1, P,
                             prefix_sharing=shared is not None,
                             prefill_chunk=args.prefill_chunk,
-                            kv_cache=args.kv_cache)
+                            kv_cache=args.kv_cache,
+                            fp8_prefill=args.fp8_prefill)
 
     def timed(fn):
         start = torch.cuda.Event(enable_timing=True)
@@ -225,20 +227,28 @@ def main():
                         "attention linears and experts): bf16, or fp8 e4m3 "
                         "rows with an fp32 scale each (W8A16 GEMV kernels; "
                         "prefill stays bf16)")
+    p.add_argument("--fp8-prefill", action="store_true",
+                   help="with --paged --kv-cache fp8: PagedBatcher("
+                        "fp8_prefill=True), which lets --shared-prefix, "
+                        "--prefill-chunk and --admit-many run over fp8 pages")
     p.add_argument("--kv-cache", choices=["bf16", "fp8"], default="bf16",
                    help="KV cache or page pools: bf16, or fp8 e4m3 rows with "
                         "an fp32 scale per (token, kv head) "
                         "(decode_attn_fp8kv.hip, paged_attn_fp8kv.hip; with "
-                        "--paged not with --prefill-chunk, --shared-prefix "
-                        "or --admit-many)")
+                        "--paged, --prefill-chunk, --shared-prefix and "
+                        "--admit-many need --fp8-prefill)")
     args = p.parse_args()
-    if args.kv_cache == "fp8" and (args.prefill_chunk is not None
-                                   or args.shared_prefix is not None
-                                   or args.admit_many):
-        print("--kv-cache fp8 has no --prefill-chunk, --shared-prefix or "
-              "--admit-many: the paged prefill kernels read bf16 pages",
-              file=sys.stderr)
+    if args.fp8_prefill and not (args.paged and args.kv_cache == "fp8"):
+        print("--fp8-prefill needs --paged --kv-cache fp8", file=sys.stderr)
         return 1
+    if args.kv_cache == "fp8" and not args.fp8_prefill and (
+            args.prefill_chunk is not None or args.shared_prefix is not None
+            or args.admit_many):
+        print("--kv-cache fp8 needs --fp8-prefill for --prefill-chunk, "
+              "--shared-prefix or --admit-many", file=sys.stderr)
+        return 1
+    if args.fp8_prefill:
+        args.batcher = True
     if args.moe_decode is not None:
         from torchx_amd import ops
 

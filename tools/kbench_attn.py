@@ -121,6 +121,47 @@ def _show(label, res, base):
     print(f"{label}: " + " | ".join(parts + ratios))
 
 
+def bench_paged_prefill_fp8kv(iters, rounds=5):
+    """The fp8-page prefill kernels against the bf16 ones on the same
+    logical rows (the fp8 pools hold quantize_kv_rows of the bf16 pools),
+    H32/8, P16: [B, S] at B4 S4096 ctx 0 and at B1 S512 behind ctx 3584,
+    and the ragged form over 4 rows of 512. The two alternate within each
+    round."""
+    dev = torch.device("cuda", 0)
+    Hq, Hkv, D, P = 32, 8, 128, 16
+    for label, B, S, c in (("B4 S4096 ctx0", 4, 4096, 0),
+                           ("B1 S512 ctx3584", 1, 512, 3584),
+                           ("ragged 4x512 ctx0", 4, 512, 0)):
+        torch.manual_seed(0)
+        M = (c + S) // P
+        table = (torch.randperm(B * M) + 1).to(torch.int32).reshape(B, M)
+        table = table.to(dev)
+        kpool = torch.randn(B * M + 1, P, Hkv, D, device=dev,
+                            dtype=torch.bfloat16)
+        vpool = torch.randn_like(kpool)
+        (k8, ks), (v8, vs) = (ops.quantize_kv_rows(x) for x in (kpool, vpool))
+        ctx = torch.full((B,), c, dtype=torch.int32, device=dev)
+        if label.startswith("ragged"):
+            q = torch.randn(B * S, Hq, D, device=dev, dtype=torch.bfloat16)
+            plan = ops.RaggedPlan([S] * B, dev, ctx=[c] * B)
+            fns = {
+                "bf16": lambda: ops.paged_prefill_attention_ragged(
+                    q, kpool, vpool, table, plan.q_lens, ctx, plan=plan),
+                "fp8": lambda: ops.paged_prefill_attention_ragged_fp8kv(
+                    q, k8, v8, ks, vs, table, plan.q_lens, ctx, plan=plan)}
+        else:
+            q = torch.randn(B, S, Hq, D, device=dev, dtype=torch.bfloat16)
+            fns = {
+                "bf16": lambda: ops.paged_prefill_attention(
+                    q, kpool, vpool, table, ctx),
+                "fp8": lambda: ops.paged_prefill_attention_fp8kv(
+                    q, k8, v8, ks, vs, table, ctx)}
+        err = (fns["fp8"]().float() - fns["bf16"]().float()).abs().max()
+        n = iters if S >= 4096 else iters * 20
+        _show(f"{label} H{Hq}/{Hkv} P{P} (max |fp8 - bf16| {err:.3f})",
+              _alternate(fns, n, rounds), "bf16")
+
+
 def bench_paged_prefill_ragged(iters, rounds=5):
     """paged_prefill_attn_ragged (tiles heaviest first, and sequence by
     sequence) against paged_prefill_attn on the same pools, ctx = 0,
@@ -328,7 +369,8 @@ def main():
     p.add_argument("--iters", type=int, default=20)
     p.add_argument("--mode", type=str, default="both",
                    choices=["fwd", "bwd", "both", "fwd-map", "paged-prefill",
-                            "paged-prefill-ragged", "decode"],
+                            "paged-prefill-ragged", "paged-prefill-fp8kv",
+                            "decode"],
                    help="fwd-map: time attn_fwd at --B/--S/--Hq/--Hkv "
                         "under each block map (ops.set_attn_fwd_map) in "
                         "one process; paged-prefill: time paged_prefill_attn at ctx=0 "
@@ -356,6 +398,9 @@ def main():
         return
     if args.mode == "decode":
         bench_decode(args.iters)
+        return
+    if args.mode == "paged-prefill-fp8kv":
+        bench_paged_prefill_fp8kv(args.iters)
         return
     if args.mode == "paged-prefill-ragged":
         bench_paged_prefill_ragged(args.iters)

@@ -227,9 +227,11 @@ class Fp8PagedKVCache:
     """One layer's paged KV pool in fp8: ``PagedKVCache``'s pages, page 0
     the dump page, holding ``Fp8KVCache``'s rows (e4m3 bytes plus one fp32
     scale per (token, kv head)), 4 KB + 64 B per Llama-3-8B token row.
-    Filled by ``ops.paged_kv_quantize_store`` (prefill) and
+    Filled by ``ops.paged_kv_quantize_store`` (prefill),
+    ``ops.paged_prefill_rope_cache_fp8kv`` (ragged prefill) and
     ``ops.paged_decode_rope_cache_fp8kv`` (decode), read by
-    ``ops.paged_decode_attention_fp8kv``. The pools start as zeros with zero
+    ``ops.paged_decode_attention_fp8kv`` and the two
+    ``ops.paged_prefill_attention*_fp8kv``. The pools start as zeros with zero
     scales: a retired row attends row 0 of page 0, which nothing but other
     retired rows ever writes, and a zero row stays finite."""
     k8pool: torch.Tensor  # [num_pages, P, Hkv, 128] float8_e4m3fn
@@ -270,8 +272,14 @@ class Fp8PagedKVCache:
         """Quantise a prefilled prefix into the pages of its row(s), rows
         chosen as ``PagedKVCache.store_prefix`` chooses them: one kernel,
         no host sync."""
+        self.store_rows(k, v, 0)
+
+    def store_rows(self, k: torch.Tensor, v: torch.Tensor,
+                   start: int) -> None:
+        """``store_prefix`` at an offset: the quantised k, v [B, S, Hkv, D]
+        become the logical rows ``start .. start+S-1`` of the same row(s)."""
         ops.paged_kv_quantize_store(k, v, *self.pools,
-                                    self.table_rows(k.shape[0]), 0)
+                                    self.table_rows(k.shape[0]), start)
 
     table_rows = PagedKVCache.table_rows
 
@@ -398,17 +406,24 @@ def prefill_extend(model, tokens: torch.Tensor, caches: list,
     roped K/V go into the pages (``store_rows``) and attention runs over
     the block table (``ops.paged_prefill_attention``), so the cached rows
     are neither recomputed nor copied. Returns the last position's logits
-    [B, vocab]. ``ctx = 0`` with the whole prompt is a paged ``prefill``."""
+    [B, vocab]. ``ctx = 0`` with the whole prompt is a paged ``prefill``.
+    ``Fp8PagedKVCache`` caches store the quantised rows and attend them
+    (``ops.paged_prefill_attention_fp8kv``), the chunk's own included,
+    where ``prefill`` attends the fresh bf16 K/V."""
     B, S = tokens.shape
     assert ctx >= 0 and S >= 1
     assert ctx + S <= model.rope_cos.shape[0], "beyond the rope tables"
     ctx_dev = torch.full((B,), ctx, dtype=torch.int32, device=tokens.device)
 
     def attend(cache, q, k, v):
-        assert isinstance(cache, PagedKVCache), "paged caches only"
+        assert isinstance(cache, (PagedKVCache, Fp8PagedKVCache)), \
+            "paged caches only"
         assert ctx + S <= cache.block_table.shape[1] * cache.page_size, \
             "beyond the block table"
         cache.store_rows(k, v, ctx)
+        if isinstance(cache, Fp8PagedKVCache):
+            return ops.paged_prefill_attention_fp8kv(
+                q, *cache.pools, cache.table_rows(B), ctx_dev)
         return ops.paged_prefill_attention(q, cache.kpool, cache.vpool,
                                            cache.table_rows(B), ctx_dev)
 
@@ -437,7 +452,8 @@ class RaggedPass:
         assert len(rows) == len(q_lens) == len(ctx) >= 1
         assert min(q_lens) >= 1 and min(ctx) >= 0
         cache = caches[0]
-        assert isinstance(cache, PagedKVCache), "paged caches only"
+        assert isinstance(cache, (PagedKVCache, Fp8PagedKVCache)), \
+            "paged caches only"
         P = cache.page_size
         ends = [c + n for c, n in zip(ctx, q_lens)]
         assert max(ends) <= model.rope_cos.shape[0], "beyond the rope tables"
@@ -459,20 +475,26 @@ class RaggedPass:
                           dev([e - 1 for e in plan.cu[1:]], torch.long))
 
 
-def _ragged_attention(model, blk, cache: PagedKVCache, x: torch.Tensor,
+def _ragged_attention(model, blk, cache, x: torch.Tensor,
                       rp: RaggedPass) -> torch.Tensor:
     """Attention half of a block over packed tokens x [1, T, H]: rope and
-    page append in one dispatch, ragged attention over the block table."""
+    page append in one dispatch, ragged attention over the block table;
+    the fp8 ops of both for an ``Fp8PagedKVCache``."""
     cfg = model.cfg
-    assert isinstance(cache, PagedKVCache), "paged caches only"
     T = x.shape[1]
     xn = ops.rmsnorm(x, blk.attn_norm, cfg.rms_eps)
-    q = ops.paged_prefill_rope_cache(
-        blk.wqkv(xn).reshape(T, -1), cache.kpool, cache.vpool,
-        model.rope_cos, model.rope_sin, rp.pos, rp.slot, cfg.num_heads)
-    attn = ops.paged_prefill_attention_ragged(
-        q, cache.kpool, cache.vpool, rp.table, rp.q_lens, rp.ctx,
-        plan=rp.plan)
+    if isinstance(cache, Fp8PagedKVCache):
+        pools = cache.pools
+        append = ops.paged_prefill_rope_cache_fp8kv
+        attend = ops.paged_prefill_attention_ragged_fp8kv
+    else:
+        assert isinstance(cache, PagedKVCache), "paged caches only"
+        pools = (cache.kpool, cache.vpool)
+        append = ops.paged_prefill_rope_cache
+        attend = ops.paged_prefill_attention_ragged
+    q = append(blk.wqkv(xn).reshape(T, -1), *pools, model.rope_cos,
+               model.rope_sin, rp.pos, rp.slot, cfg.num_heads)
+    attn = attend(q, *pools, rp.table, rp.q_lens, rp.ctx, plan=rp.plan)
     return x + blk.wo(attn.reshape(1, T, cfg.q_dim))
 
 
@@ -492,8 +514,9 @@ def prefill_ragged(model, tokens: torch.Tensor, caches: list,
     ``q_lens`` and ``ctx`` are host lists. The per-token ops see a
     [1, T] batch; ``ops.paged_prefill_rope_cache`` appends every token's
     K/V before ``ops.paged_prefill_attention_ragged`` runs, so a sequence
-    may read pages another sequence of the same pass fills. Returns the
-    logits of each sequence's last token, [B, vocab]."""
+    may read pages another sequence of the same pass fills.
+    ``Fp8PagedKVCache`` caches run the two ops' ``_fp8kv`` forms. Returns
+    the logits of each sequence's last token, [B, vocab]."""
     cfg = model.cfg
     rp = RaggedPass.build(model, caches, rows, q_lens, ctx, tokens.device)
     assert tokens.dim() == 1 and tokens.numel() == rp.plan.T
@@ -838,8 +861,15 @@ class PagedBatcher(_Batcher):
     the bytes per token row): ``admit`` (the whole-prompt path), ``step``,
     ``retire`` and preemption work as for bf16, and ``step`` sizes the
     attention split for the longest live row. ``prefix_sharing``,
-    ``prefill_chunk`` and ``admit_many`` are refused with fp8 pools: their
-    paged prefill kernels read bf16 pages.
+    ``prefill_chunk`` and ``admit_many`` are refused with fp8 pools unless
+    ``fp8_prefill=True`` opts in to the fp8 paged prefill kernels
+    (``prefill_extend`` / ``prefill_ragged`` over ``Fp8PagedKVCache``).
+    Through them a prompt row attends the QUANTISED K/V of its own chunk,
+    as decode does, where the whole-prompt ``admit`` attends the fresh bf16
+    K/V: a batcher with the opt-in is self-consistent (``admit_many``
+    leaves what sequential ``admit`` calls leave) but is not token for
+    token the dense fp8 ``ContinuousBatcher``. With the opt-in every
+    ``admit`` takes the extend path, so the two never mix in one batcher.
 
     The model may be a Llama or a Mixtral: the passes tell them apart by
     the block. ``prefill_fn``, ``decode_fn``, ``extend_fn`` and
@@ -852,13 +882,18 @@ class PagedBatcher(_Batcher):
                  page_size: int = 16, prefill_fn=None, decode_fn=None,
                  prefix_sharing: bool = False,
                  prefill_chunk: Optional[int] = None, extend_fn=None,
-                 ragged_fn=None, kv_cache: str = "bf16"):
+                 ragged_fn=None, kv_cache: str = "bf16",
+                 fp8_prefill: bool = False):
         assert kv_cache in KV_CACHE_KINDS, \
             f"kv_cache must be one of {KV_CACHE_KINDS}, got {kv_cache!r}"
         self.fp8kv = kv_cache == "fp8"
+        assert self.fp8kv or not fp8_prefill, \
+            "fp8_prefill needs kv_cache='fp8'"
+        self.fp8_prefill = fp8_prefill
         for name, on in (("prefix_sharing", prefix_sharing),
                          ("prefill_chunk", prefill_chunk is not None)):
-            assert not (self.fp8kv and on), self._no_fp8_prefill(name)
+            assert not (self.fp8kv and on) or fp8_prefill, \
+                self._no_fp8_prefill(name)
         super().__init__(model, max_batch, max_len, prefill_fn, decode_fn)
         self._extend = extend_fn or prefill_extend
         self._ragged = ragged_fn or prefill_ragged
@@ -886,9 +921,10 @@ class PagedBatcher(_Batcher):
 
     @staticmethod
     def _no_fp8_prefill(what: str) -> str:
-        return (f"{what} needs kv_cache='bf16': it runs prefill_extend / "
-                "prefill_ragged, whose MFMA paged prefill kernels read bf16 "
-                "pages; the fp8 prefill kernels over fp8 pages are missing")
+        return (f"{what} with kv_cache='fp8' needs fp8_prefill=True: it "
+                "runs prefill_extend / prefill_ragged through the fp8 "
+                "prefill kernels, where a prompt row attends the quantised "
+                "K/V of its own chunk, unlike the whole-prompt admit")
 
     def free_pages(self) -> int:
         return self.allocator.num_free
@@ -902,7 +938,8 @@ class PagedBatcher(_Batcher):
         assert not self.active[row], f"row {row} is occupied"
         S0 = prompt.numel()
         assert S0 + 1 < self.max_len
-        if self.prefix_sharing or self.prefill_chunk is not None:
+        if self.prefix_sharing or self.prefill_chunk is not None \
+                or self.fp8_prefill:
             return self._admit_extend(row, prompt)
         self._set_pages(
             row, self.allocator.alloc(-(-(S0 + 1) // self.page_size)))
@@ -1022,7 +1059,8 @@ class PagedBatcher(_Batcher):
         pass: the prompts are packed greedily in call order and split
         across passes where needed, so every token of i is in the same
         or an earlier pass than any token of j > i."""
-        assert not self.fp8kv, self._no_fp8_prefill("admit_many")
+        assert not self.fp8kv or self.fp8_prefill, \
+            self._no_fp8_prefill("admit_many")
         rows = [int(r) for r in rows]
         assert len(rows) == len(prompts) >= 1
         assert len(set(rows)) == len(rows), "rows must be distinct"

@@ -1216,6 +1216,101 @@ def paged_kv_quantize_store(k: torch.Tensor, v: torch.Tensor,
             pools[pages, t % P] = xs[b]
 
 
+def paged_prefill_attention_fp8kv(q: torch.Tensor, k8pool: torch.Tensor,
+                                  v8pool: torch.Tensor, kspool: torch.Tensor,
+                                  vspool: torch.Tensor,
+                                  block_table: torch.Tensor,
+                                  ctx: torch.Tensor,
+                                  scale: Optional[float] = None
+                                  ) -> torch.Tensor:
+    """``paged_prefill_attention`` over paged fp8 pools: q [B, S, Hq, 128]
+    holds the rows at positions ``ctx[b] ..`` of sequence b, whose
+    ``ctx[b] + S`` quantised rows (the chunk's own included) the pools
+    already hold -> o [B, S, Hq, 128]. On the GPU the e4m3 bytes reach the
+    bf16 MFMA unscaled (exact) and the row scales are applied in fp32, to
+    the score and to P; the error against fp64 attention over the
+    dequantised rows is bounded by ``bounds.prefill_fp8kv_ref_bound``."""
+    if scale is None:
+        scale = 1.0 / math.sqrt(q.shape[-1])
+    if _on_gpu(q):
+        return hip_ops().paged_prefill_attn_fp8kv(
+            q.contiguous(), k8pool, v8pool, kspool, vspool, block_table,
+            ctx.contiguous(), scale)
+    S = q.shape[1]
+    outs = []
+    for b in range(q.shape[0]):
+        c = int(ctx[b].item())
+        k8, v8, ks, vs = _paged_gather_fp8kv(k8pool, v8pool, kspool, vspool,
+                                             block_table[b], c + S)
+        outs.append(reference.attention_prefix(
+            q[b:b + 1], dequantize_kv(k8, ks), dequantize_kv(v8, vs), c,
+            scale))
+    return torch.cat(outs, dim=0)
+
+
+def paged_prefill_attention_ragged_fp8kv(q: torch.Tensor,
+                                         k8pool: torch.Tensor,
+                                         v8pool: torch.Tensor,
+                                         kspool: torch.Tensor,
+                                         vspool: torch.Tensor,
+                                         block_table: torch.Tensor, q_lens,
+                                         ctx: torch.Tensor,
+                                         scale: Optional[float] = None,
+                                         plan: Optional[RaggedPlan] = None
+                                         ) -> torch.Tensor:
+    """``paged_prefill_attention_ragged`` over paged fp8 pools: q
+    [T, Hq, 128] packed, the same ``q_lens`` / ``ctx`` / ``RaggedPlan``
+    contract. On the GPU sequence b's rows are bit-identical to
+    ``paged_prefill_attention_fp8kv`` on that sequence alone, at every
+    ctx."""
+    if scale is None:
+        scale = 1.0 / math.sqrt(q.shape[-1])
+    if plan is None:
+        plan = RaggedPlan(q_lens, q.device)
+    assert plan.q_lens == [int(n) for n in q_lens], "plan of other lengths"
+    assert q.dim() == 3 and q.shape[0] == plan.T, (q.shape, plan.T)
+    assert block_table.shape[0] == len(plan.q_lens) == ctx.numel()
+    if _on_gpu(q):
+        return hip_ops().paged_prefill_attn_ragged_fp8kv(
+            q.contiguous(), k8pool, v8pool, kspool, vspool,
+            block_table.contiguous(), ctx.contiguous(), plan.tiles, scale)
+    return torch.cat([
+        paged_prefill_attention_fp8kv(
+            q[plan.cu[b]:plan.cu[b] + n][None], k8pool, v8pool, kspool,
+            vspool, block_table[b:b + 1], ctx[b:b + 1], scale)[0]
+        for b, n in enumerate(plan.q_lens)], dim=0)
+
+
+def paged_prefill_rope_cache_fp8kv(qkv: torch.Tensor, k8pool: torch.Tensor,
+                                   v8pool: torch.Tensor, kspool: torch.Tensor,
+                                   vspool: torch.Tensor, cos: torch.Tensor,
+                                   sin: torch.Tensor, pos: torch.Tensor,
+                                   slot: torch.Tensor,
+                                   num_heads: int) -> torch.Tensor:
+    """``paged_prefill_rope_cache`` over paged fp8 pools: the same roped q
+    [T, Hq, 128], bit for bit; the roped, bf16-rounded k and the raw v of
+    token t are quantised (``quantize_kv_rows``) into pool row ``slot[t]``
+    with their scales."""
+    if _on_gpu(qkv):
+        return hip_ops().paged_prefill_rope_cache_fp8kv(
+            qkv.contiguous(), k8pool, v8pool, kspool, vspool, cos, sin,
+            pos.contiguous(), slot.contiguous())
+    # CPU: the bf16 op into one scratch row per token, then the pool rows
+    T = qkv.shape[0]
+    Hkv, D = k8pool.shape[2], k8pool.shape[3]
+    kc = torch.zeros(T, 1, Hkv, D, dtype=qkv.dtype)
+    vc = torch.zeros_like(kc)
+    q = paged_prefill_rope_cache(qkv, kc, vc, cos, sin, pos,
+                                 torch.arange(T, dtype=torch.int32),
+                                 num_heads)
+    rows = slot.long()
+    for x, pool8, pools in ((kc, k8pool, kspool), (vc, v8pool, vspool)):
+        x8, xs = quantize_kv_rows(x[:, 0])
+        pool8.view(torch.uint8).view(-1, Hkv, D)[rows] = x8.view(torch.uint8)
+        pools.view(-1, Hkv)[rows] = xs
+    return q
+
+
 def decode_linear(x: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
     """Skinny-M linear for the decode path: x [..., M, K] with M <= 8
     total rows -> x @ w.T via the W-stream-bound ``gemv_bf16`` kernel

@@ -111,13 +111,17 @@ def _lengths(S: int, T: int, causal: bool, ctx, B: int):
 
 def attention_fwd_ref_bound(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
                             scale: float, causal: bool, ctx=None,
-                            p_bf16: bool = True) -> Dict[str, torch.Tensor]:
+                            p_bf16: bool = True,
+                            extra_round: float = 0.0
+                            ) -> Dict[str, torch.Tensor]:
     """q [B,S,Hq,D], k/v [B,T,Hkv,D] (bf16 values) -> fp64 ``o`` [B,S,Hq,D],
     ``lse`` [B,Hq,S] and their elementwise bounds ``o_bound``, ``lse_bound``.
 
     ``ctx`` (ints [B]) puts q row i of sequence b at position ctx[b] + i of
     its ctx[b] + S keys (paged prefill; decode is S = 1, ctx = L - 1).
-    ``p_bf16`` says whether the kernel rounds P to bf16 (decode does not)."""
+    ``p_bf16`` says whether the kernel rounds P to bf16 (decode does not).
+    ``extra_round`` widens ``o_bound`` by one more rounding of that relative
+    size on the score and one on P (the fp8 KV kernels' row scales)."""
     B, S, Hq, _ = q.shape
     T, Hkv = k.shape[1], k.shape[2]
     G = Hq // Hkv
@@ -135,7 +139,8 @@ def attention_fwd_ref_bound(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
     o = p @ vf
     a = p @ vf.abs()
     first = 2 * U if p_bf16 else U
-    o_bound = (first + 2 * E32 * sabs_max)[..., None] * a
+    o_bound = (first + extra_round +
+               2 * (E32 + extra_round) * sabs_max)[..., None] * a
     lse_bound = 2 * E32 * sabs_max + 2.0 ** -20 * (1 + lse.abs())
     return {
         "o": o.permute(0, 2, 1, 3).contiguous(),
@@ -202,6 +207,27 @@ def decode_fp8kv_ref_bound(q: torch.Tensor, k8: torch.Tensor,
     o_bound = (U + r23 + 2 * (E32 + r23) * sabs_max)[..., None] * (
         p @ vf.abs())
     return {"o": (p @ vf)[:, :, 0], "o_bound": o_bound[:, :, 0]}
+
+
+def prefill_fp8kv_ref_bound(q: torch.Tensor, k8: torch.Tensor,
+                            v8: torch.Tensor, ks: torch.Tensor,
+                            vs: torch.Tensor, scale: float,
+                            ctx) -> Dict[str, torch.Tensor]:
+    """Paged prefill over fp8 rows: q [B,S,Hq,D] bf16 behind ctx[b] rows of
+    the gathered k8/v8 [B,T,Hkv,D] e4m3, ks/vs [B,T,Hkv] -> fp64 ``o``
+    [B,S,Hq,D] and ``o_bound``.  The reference is
+    ``attention_fwd_ref_bound`` on the dequantised rows k' = k8 ks,
+    v' = v8 vs, and the bound is its forward bound widened by the two fp32
+    roundings ``decode_fp8kv_ref_bound`` derives, (ks_j sc2) acc_ij and
+    p_ij vs_j in front of the bf16 pack:
+
+      |o - o64|_id <= (2u + 2^-23 + 2 (e32 + 2^-23) max_j sabs_ij)
+                      sum_j p_ij |v'_jd|,     sabs on k'."""
+    kd = k8.double() * ks[..., None].double()
+    vd = v8.double() * vs[..., None].double()
+    r = attention_fwd_ref_bound(q, kd, vd, scale, True, ctx=ctx,
+                                extra_round=2.0 ** -23)
+    return {"o": r["o"], "o_bound": r["o_bound"]}
 
 
 # ---------------------------------------------------------------------------

@@ -22,7 +22,9 @@
 //  * paged_prefill_attn_kernel: the 4-wave forward over a block-table KV
 //    cache, for a chunk of query rows behind an already cached prefix;
 //    paged_prefill_attn_ragged_kernel: the same block work over a packed
-//    batch of chunks of different lengths (host-built tile list).
+//    batch of chunks of different lengths (host-built tile list). Their
+//    _fp8kv twins read e4m3 pages with fp32 row scales, converted to the
+//    same bf16 LDS images once per block on the stage.
 //  * Backward is FA2-style without atomics: preprocess delta =
 //    rowsum(dO*O); ONE dK+dV kernel, 4 waves at one wave per SIMD, in
 //    which a wave accumulates both dK and dV for its 32 kv rows (S, P and
@@ -804,6 +806,371 @@ paged_prefill_attn_ragged_kernel(
   paged_prefill_tile(q + seq_off, kpool + (long)hkv * HD,
                      vpool + (long)hkv * HD, o + seq_off, bt + (long)b * M,
                      ctx[b], S, qt, Hq, Hkv, num_pages, logP, M, scale, smem);
+}
+
+// ---------------------------------------------------------------------------
+// Paged prefill over fp8 (OCP e4m3) pages: the two kernels above for the
+// pools of Fp8PagedKVCache.
+//
+//   k8pool/v8pool  [num_pages, P, Hkv, 128] e4m3
+//   kspool/vspool  [num_pages, P, Hkv] fp32      value = k8 * ks
+//
+// Work split, block maps, masking and the ctx / cap / L clamping are
+// paged_prefill_tile's; so are the LDS images, which still hold bf16: a
+// tile is converted ONCE per block, on the stage, and the MFMA and
+// transpose-read body runs unchanged on it. Converting at the fragment
+// read would have each of the 4 waves convert the whole 64 x 128 tile for
+// K and again for V, in a kernel whose critical resource is the softmax
+// VALU.
+//
+// Staging of one 64-row tile: wave w owns the rows [16w, 16w+16) (one page,
+// one table entry, as in the bf16 kernel), 8 lanes per 128-byte row, two
+// rows per lane: four 16-byte global loads (2 K, 2 V) per thread, and one
+// scale in lanes 0..31 (K rows in 0..15, V rows in 16..31). The loads of
+// tile t+1 go out before the compute of tile t and wait in 17 VGPRs; after
+// the compute each chunk goes through 8 v_cvt_scalef32_pk_bf16_fp8 (scale
+// 1.0: every e4m3 value is exact in bf16) and is written as two 16-byte
+// ds_write into the XOR-swizzled image of the other buffer, which every
+// wave left at the previous barrier. This gives up the async
+// global_load_lds for half the global bytes.
+//
+// Numerics. The row scales never touch the bf16 operands:
+//   s_jq = (ks_j * scale * log2e) * acc_jq   ks_j * sc2 is formed once by
+//          the staging lane and read back from LDS [2][2][64], 4 rows of
+//          the accumulator order per ds_read_b128 (broadcast);
+//   PV operand = bf16(p_jq * vs_j), l_run sums the unscaled p.
+// Rows at or past L read last_row, bytes and scales, so no pool row
+// outside the sequence reaches a register; a zero row under a zero scale
+// (the dump page) gives score 0 and value 0.
+// ---------------------------------------------------------------------------
+typedef __bf16 mbf16x2 __attribute__((ext_vector_type(2)));
+
+#define SC_FLOATS (2 * FKV)  // one buffer of tile scales: K rows, V rows
+
+// A lane's share of one staged tile on its way from the pools to LDS.
+struct Fp8TileRegs {
+  uint4_v k[2], v[2];
+  float s;
+};
+
+// 8 e4m3 bytes -> 8 bf16, element order kept.
+__device__ __forceinline__ uint4_v fp8x8_to_bf16x8(unsigned int a,
+                                                   unsigned int b) {
+  const mbf16x2 p0 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(a, 1.0f, false);
+  const mbf16x2 p1 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(a, 1.0f, true);
+  const mbf16x2 p2 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(b, 1.0f, false);
+  const mbf16x2 p3 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(b, 1.0f, true);
+  return uint4_v{__builtin_bit_cast(unsigned int, p0),
+                 __builtin_bit_cast(unsigned int, p1),
+                 __builtin_bit_cast(unsigned int, p2),
+                 __builtin_bit_cast(unsigned int, p3)};
+}
+
+// Pool row (in rows of [Hkv]) of tile row `row`: through the group's page,
+// or the sequence's last row at or past L.
+__device__ __forceinline__ long fp8_tile_src_row(int kv0, int row, int L,
+                                                 int pmask, long grp_base,
+                                                 long last_row) {
+  const int t = kv0 + row;
+  return t >= L ? last_row : grp_base + (t & pmask);
+}
+
+// Issue the loads of the tile at kv0. `kb` / `vb` point at the kv head's
+// bytes in pool row 0, `ksb` / `vsb` at its scale there.
+__device__ __forceinline__ void fp8_tile_load(
+    Fp8TileRegs& tr, const unsigned char* __restrict__ kb,
+    const unsigned char* __restrict__ vb, const float* __restrict__ ksb,
+    const float* __restrict__ vsb, int kv0, int Hkv, int L, int pmask,
+    long grp_base, long last_row) {
+  const int wave = threadIdx.x / 64;
+  const int lane = threadIdx.x & 63;
+  #pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    const int row = wave * (FKV / 4) + j * 8 + (lane >> 3);
+    const long off =
+        fp8_tile_src_row(kv0, row, L, pmask, grp_base, last_row) * Hkv * HD +
+        (lane & 7) * 16;
+    tr.k[j] = *(const uint4_v*)(kb + off);
+    tr.v[j] = *(const uint4_v*)(vb + off);
+  }
+  if (lane < 32) {
+    const long srow = fp8_tile_src_row(kv0, wave * (FKV / 4) + (lane & 15), L,
+                                       pmask, grp_base, last_row);
+    tr.s = ((lane & 16) ? vsb : ksb)[srow * Hkv];
+  }
+}
+
+// Convert and write a lane's share into the bf16 images and the scale
+// buffer `sc` ([0, 64): ks * sc2, [64, 128): vs).
+__device__ __forceinline__ void fp8_tile_store(const Fp8TileRegs& tr,
+                                               char* kimg, char* vimg,
+                                               float* sc, float sc2) {
+  const int wave = threadIdx.x / 64;
+  const int lane = threadIdx.x & 63;
+  #pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    const int row = wave * (FKV / 4) + j * 8 + (lane >> 3);
+    const int byte = ((lane & 7) * 32) ^ ((row & 15) << 4);
+    char* kd = kimg + row * 256;
+    char* vd = vimg + row * 256;
+    *(uint4_v*)(kd + byte) = fp8x8_to_bf16x8(tr.k[j][0], tr.k[j][1]);
+    *(uint4_v*)(kd + (byte ^ 16)) = fp8x8_to_bf16x8(tr.k[j][2], tr.k[j][3]);
+    *(uint4_v*)(vd + byte) = fp8x8_to_bf16x8(tr.v[j][0], tr.v[j][1]);
+    *(uint4_v*)(vd + (byte ^ 16)) = fp8x8_to_bf16x8(tr.v[j][2], tr.v[j][3]);
+  }
+  if (lane < 32) {
+    const int row = wave * (FKV / 4) + (lane & 15);
+    if (lane & 16) sc[FKV + row] = tr.s;
+    else sc[row] = tr.s * sc2;
+  }
+}
+
+// paged_prefill_tile for fp8 pools; `sc_lds` is the [2][SC_FLOATS] scale
+// buffer. All four waves run every barrier.
+__device__ __forceinline__ void paged_prefill_tile_fp8kv(
+    const unsigned short* __restrict__ qb,
+    const unsigned char* __restrict__ kb,
+    const unsigned char* __restrict__ vb,
+    const float* __restrict__ ksb, const float* __restrict__ vsb,
+    unsigned short* __restrict__ ob,
+    const int* __restrict__ bt_row, int ctx_b, int S, int qt, int Hq,
+    int Hkv, int num_pages, int logP, int M, float scale, char* smem,
+    float* sc_lds) {
+  const int BQ = 4 * QBLK;
+
+  const int wave = threadIdx.x / 64;
+  const int lane = threadIdx.x & 63;
+  const bool hi = lane >= 32;
+  const int qr = lane & 31;
+
+  // the clamping of paged_prefill_tile
+  const int cap = M << logP;
+  const int c0 = min(max(ctx_b, 0), cap);
+  const int L = (S > cap - c0) ? cap : c0 + S;
+  const int pmask = (1 << logP) - 1;
+
+  const long q_seq_stride = (long)Hq * HD;
+
+  const int q0_blk = qt * BQ;
+  const int qw0 = q0_blk + wave * QBLK;       // wave's first q row
+  const long q_row = qw0 + qr;                 // this lane's q row
+  const bool wave_active = qw0 < S;
+
+  mbf16x8 qfrag[8];
+  {
+    const long row = (q_row < S) ? q_row : (S - 1);
+    const unsigned short* qp = qb + row * q_seq_stride + (hi ? 8 : 0);
+    #pragma unroll
+    for (int c = 0; c < 8; ++c) {
+      qfrag[c] = __builtin_bit_cast(mbf16x8, *(const ushort8*)(qp + c * 16));
+    }
+  }
+
+  f32x16 acc_o[4] = {};
+  float m_run = -3.0e38f, l_run = 0.f;   // m in exp2 domain
+  const float sc2 = scale * LOG2E;
+
+  const int kv_limit = min(L, c0 + q0_blk + BQ);
+  const int ntiles = (kv_limit + FKV - 1) / FKV;
+  const int qw_max = min(qw0 + QBLK - 1, S - 1);
+
+  char* k0 = smem;                       // K tile t   (cur)
+  char* k1 = smem + KIMG_BYTES;          // K tile t+1 (being written)
+  char* vcur = smem + 2 * KIMG_BYTES;
+  char* vnxt = smem + 3 * KIMG_BYTES;
+  float* scur = sc_lds;
+  float* snxt = sc_lds + SC_FLOATS;
+
+  const long last_row =
+      paged_page_base(bt_row[(L - 1) >> logP], num_pages, logP) +
+      ((L - 1) & pmask);
+
+  // prologue: tile 0 through registers; table entry of tile 1
+  Fp8TileRegs tr;
+  int ent_nxt = paged_group_entry(bt_row, FKV, L, logP);
+  fp8_tile_load(tr, kb, vb, ksb, vsb, 0, Hkv, L, pmask,
+                paged_page_base(paged_group_entry(bt_row, 0, L, logP),
+                                num_pages, logP),
+                last_row);
+  fp8_tile_store(tr, k0, vcur, scur, sc2);
+  __syncthreads();
+
+  for (int t = 0; t < ntiles; ++t) {
+    const int kv0 = t * FKV;
+    const bool has_next = (t + 1) < ntiles;
+    if (has_next) {
+      // next tile's loads BEFORE compute, through the entry fetched one
+      // iteration ago; they are first looked at after the compute
+      const long base = paged_page_base(ent_nxt, num_pages, logP);
+      ent_nxt = paged_group_entry(bt_row, kv0 + 2 * FKV, L, logP);
+      fp8_tile_load(tr, kb, vb, ksb, vsb, kv0 + FKV, Hkv, L, pmask, base,
+                    last_row);
+    }
+
+    const bool needed = wave_active && (kv0 <= c0 + qw_max);
+    if (needed) {
+      f32x16 acc0 = {}, acc1 = {};
+      __builtin_amdgcn_s_setprio(1);
+      #pragma unroll
+      for (int c = 0; c < 8; ++c) {
+        acc0 = mfma32(kimg_frag(k0, 0, c), qfrag[c], acc0);
+        acc1 = mfma32(kimg_frag(k0, 1, c), qfrag[c], acc1);
+      }
+      __builtin_amdgcn_s_setprio(0);
+
+      // registers 4g .. 4g+3 of the 32 scores are the 4 consecutive tile
+      // rows from (g >> 2) * 32 + 8 * (g & 3) + 4 * hi (c_row)
+      float sv[32];
+      #pragma unroll
+      for (int g = 0; g < 8; ++g) {
+        const f32x4 k4 = *(const f32x4*)(
+            scur + (g >> 2) * 32 + 8 * (g & 3) + (hi ? 4 : 0));
+        #pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const int r = 4 * g + j;
+          sv[r] = (r < 16 ? acc0[r] : acc1[r - 16]) * k4[j];
+        }
+      }
+      const bool mask_tile =
+          (kv0 + FKV - 1 > c0 + qw0) || (kv0 + FKV > L) || (q_row >= S);
+      if (mask_tile) {
+        #pragma unroll
+        for (int r = 0; r < 32; ++r) {
+          const long kg = kv0 + (r >> 4) * 32 + c_row(r & 15, hi);
+          if (kg >= L || q_row >= S || kg > c0 + q_row) {
+            sv[r] = -3.0e38f;
+          }
+        }
+      }
+
+      // online softmax, exp2 domain, T13 defer-max (see attn_fwd_kernel)
+      float m_tile = sv[0];
+      #pragma unroll
+      for (int r = 1; r < 32; ++r) m_tile = fmaxf(m_tile, sv[r]);
+      m_tile = fmaxf(m_tile, __shfl_xor(m_tile, 32, 64));
+      const float THR2 = 11.54f;  // 8 * log2(e)
+      if (!__all(m_tile - m_run <= THR2)) {
+        const float m_new = fmaxf(m_run, m_tile);
+        const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);
+        l_run *= alpha;
+        m_run = m_new;
+        #pragma unroll
+        for (int dt = 0; dt < 4; ++dt) {
+          #pragma unroll
+          for (int r = 0; r < 16; ++r) acc_o[dt][r] *= alpha;
+        }
+      }
+
+      float row_sum = 0.f;
+      #pragma unroll
+      for (int r = 0; r < 32; ++r) {
+        sv[r] = __builtin_amdgcn_exp2f(sv[r] - m_run);  // sv becomes P
+        row_sum += sv[r];
+      }
+      row_sum += __shfl_xor(row_sum, 32, 64);
+      l_run += row_sum;
+
+      // fold vs_j into P in front of the bf16 pack
+      #pragma unroll
+      for (int g = 0; g < 8; ++g) {
+        const f32x4 v4 = *(const f32x4*)(
+            scur + FKV + (g >> 2) * 32 + 8 * (g & 3) + (hi ? 4 : 0));
+        #pragma unroll
+        for (int j = 0; j < 4; ++j) sv[4 * g + j] *= v4[j];
+      }
+
+      mbf16x8 pf[4];
+      cvals_to_frags(sv, hi, &pf[0], &pf[1]);
+      cvals_to_frags(sv + 16, hi, &pf[2], &pf[3]);
+
+      __builtin_amdgcn_s_setprio(1);
+      #pragma unroll
+      for (int dt = 0; dt < 4; ++dt) {
+        #pragma unroll
+        for (int ks = 0; ks < 4; ++ks) {
+          acc_o[dt] = mfma32(nat_tr_frag(vcur, ks, dt), pf[ks], acc_o[dt]);
+        }
+      }
+      __builtin_amdgcn_s_setprio(0);
+    }
+
+    if (has_next) {
+      fp8_tile_store(tr, k1, vnxt, snxt, sc2);
+      __syncthreads();   // everyone done reading cur; nxt visible
+      char* tk = k0; k0 = k1; k1 = tk;
+      char* tv = vcur; vcur = vnxt; vnxt = tv;
+      float* ts = scur; scur = snxt; snxt = ts;
+    }
+  }
+
+  if (!wave_active || q_row >= S) return;
+
+  fwd_store_o(acc_o, l_run, hi, ob + q_row * q_seq_stride);
+}
+
+__global__ void __launch_bounds__(256, 2)
+paged_prefill_attn_fp8kv_kernel(const unsigned short* __restrict__ q,
+                                const unsigned char* __restrict__ k8pool,
+                                const unsigned char* __restrict__ v8pool,
+                                const float* __restrict__ kspool,
+                                const float* __restrict__ vspool,
+                                unsigned short* __restrict__ o,
+                                const int* __restrict__ bt,   // [B, M]
+                                const int* __restrict__ ctx,  // [B]
+                                int B, int S, int Hq, int Hkv, int num_pages,
+                                int logP, int M, float scale) {
+  __shared__ __align__(16) char smem[4 * KIMG_BYTES];
+  __shared__ __align__(16) float sc_lds[2 * SC_FLOATS];
+
+  const int nqt = (S + 4 * QBLK - 1) / (4 * QBLK);
+  const int G = Hq / Hkv;
+  int b, hq, qt;
+  map_block_fwd(B, Hq, Hkv, nqt, G, &b, &hq, &qt);
+  const int hkv = hq / G;
+  const long seq_off = ((long)b * S * Hq + hq) * HD;
+  paged_prefill_tile_fp8kv(q + seq_off, k8pool + (long)hkv * HD,
+                           v8pool + (long)hkv * HD, kspool + hkv,
+                           vspool + hkv, o + seq_off, bt + (long)b * M,
+                           ctx[b], S, qt, Hq, Hkv, num_pages, logP, M, scale,
+                           smem, sc_lds);
+}
+
+// The ragged form: paged_prefill_attn_ragged_kernel's unit map and tile
+// clamping around the fp8 tile body, so sequence b's rows are
+// bit-identical to paged_prefill_attn_fp8kv_kernel on that sequence alone.
+__global__ void __launch_bounds__(256, 2)
+paged_prefill_attn_ragged_fp8kv_kernel(
+    const unsigned short* __restrict__ q,      // [T, Hq, 128]
+    const unsigned char* __restrict__ k8pool,
+    const unsigned char* __restrict__ v8pool,
+    const float* __restrict__ kspool,
+    const float* __restrict__ vspool,
+    unsigned short* __restrict__ o,            // [T, Hq, 128]
+    const int* __restrict__ bt,                // [B, M]
+    const int* __restrict__ ctx,               // [B]
+    const int4* __restrict__ tiles,            // [ntiles]
+    int ntiles, int B, int T, int Hq, int Hkv, int num_pages, int logP,
+    int M, float scale) {
+  __shared__ __align__(16) char smem[4 * KIMG_BYTES];
+  __shared__ __align__(16) float sc_lds[2 * SC_FLOATS];
+
+  const int G = Hq / Hkv;
+  const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
+  const int unit = (slot / G) * 8 + xcd;
+  if (unit >= ntiles * Hkv) return;  // block-uniform: the padding units
+  const int hkv = unit % Hkv;
+  const int hq = hkv * G + slot % G;
+  const int4 td = tiles[unit / Hkv];
+  const int b = min(max(td.x, 0), B - 1);
+  const int cu = min(max(td.z, 0), T - 1);
+  const int S = min(max(td.w, 1), T - cu);
+  const int qt = min(max(td.y, 0), (S - 1) / (4 * QBLK));
+  const long seq_off = ((long)cu * Hq + hq) * HD;
+  paged_prefill_tile_fp8kv(q + seq_off, k8pool + (long)hkv * HD,
+                           v8pool + (long)hkv * HD, kspool + hkv,
+                           vspool + hkv, o + seq_off, bt + (long)b * M,
+                           ctx[b], S, qt, Hq, Hkv, num_pages, logP, M, scale,
+                           smem, sc_lds);
 }
 
 // ---------------------------------------------------------------------------
@@ -2152,6 +2519,39 @@ extern "C" void paged_prefill_attn_ragged_launch(
                      dim3(256), 0, stream, (const unsigned short*)q,
                      (const unsigned short*)kpool,
                      (const unsigned short*)vpool, (unsigned short*)o,
+                     (const int*)bt, (const int*)ctx, (const int4*)tiles,
+                     ntiles, B, T, Hq, Hkv, num_pages, logP, M, scale);
+}
+
+extern "C" void paged_prefill_attn_fp8kv_launch(
+    const void* q, const void* k8pool, const void* v8pool,
+    const void* kspool, const void* vspool, void* o, const void* bt,
+    const void* ctx, int B, int S, int Hq, int Hkv, int num_pages, int logP,
+    int M, float scale, hipStream_t stream) {
+  const int nqt = (S + 4 * QBLK - 1) / (4 * QBLK);
+  hipLaunchKernelGGL(paged_prefill_attn_fp8kv_kernel, dim3(B * Hq * nqt),
+                     dim3(256), 0, stream, (const unsigned short*)q,
+                     (const unsigned char*)k8pool,
+                     (const unsigned char*)v8pool, (const float*)kspool,
+                     (const float*)vspool, (unsigned short*)o,
+                     (const int*)bt, (const int*)ctx, B, S, Hq, Hkv,
+                     num_pages, logP, M, scale);
+}
+
+extern "C" void paged_prefill_attn_ragged_fp8kv_launch(
+    const void* q, const void* k8pool, const void* v8pool,
+    const void* kspool, const void* vspool, void* o, const void* bt,
+    const void* ctx, const void* tiles, int ntiles, int B, int T, int Hq,
+    int Hkv, int num_pages, int logP, int M, float scale,
+    hipStream_t stream) {
+  // the grid of paged_prefill_attn_ragged_launch
+  const long units = (long)ntiles * Hkv;
+  const long grid = (units + 7) / 8 * 8 * (Hq / Hkv);
+  hipLaunchKernelGGL(paged_prefill_attn_ragged_fp8kv_kernel,
+                     dim3((unsigned)grid), dim3(256), 0, stream,
+                     (const unsigned short*)q, (const unsigned char*)k8pool,
+                     (const unsigned char*)v8pool, (const float*)kspool,
+                     (const float*)vspool, (unsigned short*)o,
                      (const int*)bt, (const int*)ctx, (const int4*)tiles,
                      ntiles, B, T, Hq, Hkv, num_pages, logP, M, scale);
 }

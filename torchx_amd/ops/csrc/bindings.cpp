@@ -124,6 +124,21 @@ void paged_decode_rope_cache_fp8kv_launch(const void*, void*, void*, void*,
 void paged_kv_quantize_store_launch(const void*, const void*, void*, void*,
                                     void*, void*, const void*, int, int, int,
                                     int, int, int, int, hipStream_t);
+void paged_prefill_attn_fp8kv_launch(const void*, const void*, const void*,
+                                     const void*, const void*, void*,
+                                     const void*, const void*, int, int, int,
+                                     int, int, int, int, float, hipStream_t);
+void paged_prefill_attn_ragged_fp8kv_launch(const void*, const void*,
+                                            const void*, const void*,
+                                            const void*, void*, const void*,
+                                            const void*, const void*, int,
+                                            int, int, int, int, int, int, int,
+                                            float, hipStream_t);
+void paged_prefill_rope_cache_fp8kv_launch(const void*, void*, void*, void*,
+                                           void*, void*, const void*,
+                                           const void*, const void*,
+                                           const void*, long, int, int, long,
+                                           int, hipStream_t);
 }
 
 namespace {
@@ -1416,6 +1431,118 @@ at::Tensor paged_prefill_rope_cache(at::Tensor qkv, at::Tensor kpool,
   return q;
 }
 
+// ---- paged prefill over fp8 pools (attention.hip, paged_attn_fp8kv.hip) ----
+
+// paged_prefill_attn over fp8 pools: q [B, S, Hq, 128] behind ctx[b] cached
+// rows, k8pool / v8pool / kspool / vspool as for paged_decode_attn_fp8kv.
+at::Tensor paged_prefill_attn_fp8kv(at::Tensor q, at::Tensor k8pool,
+                                    at::Tensor v8pool, at::Tensor kspool,
+                                    at::Tensor vspool, at::Tensor bt,
+                                    at::Tensor ctx, double scale) {
+  const char* op = "paged_prefill_attn_fp8kv";
+  check_bf16(q, "q");
+  TORCH_CHECK(q.dim() == 4 && q.size(3) == 128,
+              "q must be [B, S, Hq, 128]");
+  const int B = q.size(0), Hq = q.size(2);
+  TORCH_CHECK(q.size(1) >= 1 && q.size(1) < (1L << 30), "need 1 <= S < 2^30");
+  const int S = q.size(1);
+  const int logP =
+      check_paged_fp8kv(k8pool, v8pool, kspool, vspool, bt, B, op);
+  check_paged_pos(ctx, B, op);
+  TORCH_CHECK(ctx.dim() == 1, "ctx must be int32 [B]");
+  const int num_pages = k8pool.size(0), Hkv = k8pool.size(2);
+  const int M = bt.size(1);
+  TORCH_CHECK(num_pages >= 1 && Hkv >= 1, op, ": empty pools");
+  TORCH_CHECK(Hq % Hkv == 0, "GQA group mismatch");
+  const long nqt = (S + 127) / 128;
+  TORCH_CHECK((long)B * Hq * nqt < (1L << 31), "grid too large");
+  auto o = at::empty_like(q);
+  paged_prefill_attn_fp8kv_launch(
+      q.data_ptr(), k8pool.data_ptr(), v8pool.data_ptr(), kspool.data_ptr(),
+      vspool.data_ptr(), o.data_ptr(), bt.data_ptr(), ctx.data_ptr(), B, S,
+      Hq, Hkv, num_pages, logP, M, (float)scale, cur_stream());
+  return o;
+}
+
+// paged_prefill_attn_ragged over fp8 pools: q [T, Hq, 128] packed, the same
+// int32 [ntiles, 4] tile list.
+at::Tensor paged_prefill_attn_ragged_fp8kv(at::Tensor q, at::Tensor k8pool,
+                                           at::Tensor v8pool,
+                                           at::Tensor kspool,
+                                           at::Tensor vspool, at::Tensor bt,
+                                           at::Tensor ctx, at::Tensor tiles,
+                                           double scale) {
+  const char* op = "paged_prefill_attn_ragged_fp8kv";
+  check_bf16(q, "q");
+  TORCH_CHECK(q.dim() == 3 && q.size(2) == 128, "q must be [T, Hq, 128]");
+  TORCH_CHECK(q.size(0) >= 1 && q.size(0) < (1L << 30), "need 1 <= T < 2^30");
+  const int T = q.size(0), Hq = q.size(1);
+  const int B = bt.dim() == 2 ? bt.size(0) : 0;
+  const int logP =
+      check_paged_fp8kv(k8pool, v8pool, kspool, vspool, bt, B, op);
+  check_paged_pos(ctx, B, op);
+  TORCH_CHECK(B >= 1 && ctx.dim() == 1, "ctx must be int32 [B], B >= 1");
+  TORCH_CHECK(tiles.is_cuda() && tiles.scalar_type() == at::kInt &&
+                  tiles.dim() == 2 && tiles.size(1) == 4 &&
+                  tiles.size(0) >= 1 && tiles.is_contiguous(),
+              "tiles must be a contiguous int32 [ntiles, 4] device tensor");
+  const int num_pages = k8pool.size(0), Hkv = k8pool.size(2);
+  const int M = bt.size(1);
+  TORCH_CHECK(num_pages >= 1 && Hkv >= 1, op, ": empty pools");
+  TORCH_CHECK(Hq % Hkv == 0, "GQA group mismatch");
+  const long ntiles = tiles.size(0);
+  TORCH_CHECK((ntiles * Hkv + 7) / 8 * 8 * (Hq / Hkv) < (1L << 31),
+              "grid too large");
+  auto o = at::empty_like(q);
+  paged_prefill_attn_ragged_fp8kv_launch(
+      q.data_ptr(), k8pool.data_ptr(), v8pool.data_ptr(), kspool.data_ptr(),
+      vspool.data_ptr(), o.data_ptr(), bt.data_ptr(), ctx.data_ptr(),
+      tiles.data_ptr(), (int)ntiles, B, T, Hq, Hkv, num_pages, logP, M,
+      (float)scale, cur_stream());
+  return o;
+}
+
+// paged_prefill_rope_cache over fp8 pools: the roped k and the raw v of
+// token t are quantised into pool row slot[t]; returns q [T, Hq, 128].
+at::Tensor paged_prefill_rope_cache_fp8kv(at::Tensor qkv, at::Tensor k8pool,
+                                          at::Tensor v8pool,
+                                          at::Tensor kspool,
+                                          at::Tensor vspool, at::Tensor cos_t,
+                                          at::Tensor sin_t, at::Tensor pos,
+                                          at::Tensor slot) {
+  const char* op = "paged_prefill_rope_cache_fp8kv";
+  check_bf16(qkv, "qkv");
+  check_f32(cos_t, "cos");
+  check_f32(sin_t, "sin");
+  TORCH_CHECK(qkv.dim() == 2 && qkv.size(0) >= 1,
+              "qkv must be [T, (Hq+2*Hkv)*128]");
+  const Fp8kvDims c = check_fp8kv_cache(k8pool, v8pool, kspool, vspool, op);
+  const long T = qkv.size(0);
+  const long pool_rows = (long)c.B * c.T;  // num_pages * P
+  TORCH_CHECK(pool_rows >= 1 && c.Hkv >= 1, op, ": empty pools");
+  TORCH_CHECK(pool_rows < (1L << 31), "pool too large for int32 slots");
+  for (const at::Tensor* t : {&pos, &slot}) {
+    TORCH_CHECK(t->is_cuda() && t->scalar_type() == at::kInt &&
+                    t->is_contiguous() && t->dim() == 1 && t->size(0) == T,
+                "pos/slot must be contiguous int32 [T] device tensors");
+  }
+  TORCH_CHECK(cos_t.dim() == 2 && cos_t.size(1) == 64 &&
+                  cos_t.size(0) >= 1 && sin_t.sizes() == cos_t.sizes(),
+              "cos/sin must be [S, 64] (head_dim 128)");
+  const long nh = qkv.size(1) / 128;
+  const int Hq = (int)nh - 2 * c.Hkv;
+  TORCH_CHECK(Hq >= 1 && qkv.size(1) == nh * 128, "qkv width mismatch");
+  TORCH_CHECK(Hq % c.Hkv == 0, "GQA group mismatch");
+  const int rope_rows = (int)std::min<long>(cos_t.size(0), 1L << 30);
+  auto q = at::empty({T, (long)Hq, 128}, qkv.options());
+  paged_prefill_rope_cache_fp8kv_launch(
+      qkv.data_ptr(), q.data_ptr(), k8pool.data_ptr(), v8pool.data_ptr(),
+      kspool.data_ptr(), vspool.data_ptr(), cos_t.data_ptr(),
+      sin_t.data_ptr(), pos.data_ptr(), slot.data_ptr(), T, Hq, c.Hkv,
+      pool_rows, rope_rows, cur_stream());
+  return q;
+}
+
 // ---- fused residual add + rmsnorm (inference) ------------------------------
 // s = x + res, y = rmsnorm(s) * w; returns (s, y). res omitted -> plain
 // rmsnorm (s aliases x).
@@ -1557,6 +1684,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("paged_prefill_attn", &paged_prefill_attn);
   m.def("paged_prefill_attn_ragged", &paged_prefill_attn_ragged);
   m.def("paged_prefill_rope_cache", &paged_prefill_rope_cache);
+  m.def("paged_prefill_attn_fp8kv", &paged_prefill_attn_fp8kv);
+  m.def("paged_prefill_attn_ragged_fp8kv", &paged_prefill_attn_ragged_fp8kv);
+  m.def("paged_prefill_rope_cache_fp8kv", &paged_prefill_rope_cache_fp8kv);
   m.def("rmsnorm_res", &rmsnorm_res,
         py::arg("x"), py::arg("res"), py::arg("w"), py::arg("eps"));
 }

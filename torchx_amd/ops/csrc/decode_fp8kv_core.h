@@ -28,6 +28,21 @@ __device__ __forceinline__ float kv_quant(float x, float scale) {
   return fminf(fmaxf(x / scale, -FP8_MAX), FP8_MAX);
 }
 
+// 8 floats -> 8 e4m3 bytes in element order (clamp, then two
+// v_cvt_pk_fp8_f32 pairs per 4 bytes).
+__device__ __forceinline__ uint2_v kv_quant_pack8(const float (&x)[8],
+                                                  float scale) {
+  float y[8];
+  #pragma unroll
+  for (int j = 0; j < 8; ++j) y[j] = kv_quant(x[j], scale);
+  uint2_v out;
+  out[0] = __builtin_amdgcn_cvt_pk_fp8_f32(y[0], y[1], 0u, false);
+  out[0] = __builtin_amdgcn_cvt_pk_fp8_f32(y[2], y[3], out[0], true);
+  out[1] = __builtin_amdgcn_cvt_pk_fp8_f32(y[4], y[5], 0u, false);
+  out[1] = __builtin_amdgcn_cvt_pk_fp8_f32(y[6], y[7], out[1], true);
+  return out;
+}
+
 // Prefill side, one (row, kv head) item on 16 lanes: one 16-B load (8 bf16)
 // of source row `it`, a 16-lane fmaxf butterfly, two v_cvt_pk_fp8_f32 pairs
 // per 4 bytes, one 8-B store to row `drow` of dst8 and its scale. `dl` is
@@ -49,13 +64,7 @@ __device__ __forceinline__ void kv_quantize_item(
   for (int off = 8; off >= 1; off >>= 1)
     amax = fmaxf(amax, __shfl_xor(amax, off, 16));
   const float scale = kv_row_scale(amax);
-  #pragma unroll
-  for (int j = 0; j < 8; ++j) x[j] = kv_quant(x[j], scale);
-  uint2_v out;
-  out[0] = __builtin_amdgcn_cvt_pk_fp8_f32(x[0], x[1], 0u, false);
-  out[0] = __builtin_amdgcn_cvt_pk_fp8_f32(x[2], x[3], out[0], true);
-  out[1] = __builtin_amdgcn_cvt_pk_fp8_f32(x[4], x[5], 0u, false);
-  out[1] = __builtin_amdgcn_cvt_pk_fp8_f32(x[6], x[7], out[1], true);
+  const uint2_v out = kv_quant_pack8(x, scale);
   if (live) {
     *(uint2_v*)(dst8 + drow * HD + dl * 8) = out;
     if (dl == 0) dsts[drow] = scale;

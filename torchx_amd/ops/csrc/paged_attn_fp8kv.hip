@@ -13,7 +13,9 @@
 // kernels run the bodies of decode_fp8kv_core.h, so for the same split
 // count the attention output is bit-identical to decode_attn_fp8kv_kernel on
 // the same logical cache, and both quantisers store the bytes and scales of
-// the dense ones.
+// the dense ones. A fourth kernel is the packed-token rope + quantising
+// append of the ragged prefill pass; the prefill attention over these pools
+// is in attention.hip (paged_prefill_attn_fp8kv_kernel).
 //
 // Attention: decode_attn_fp8kv_block over PagedRows8. Work split, lane map,
 // loop structure, arithmetic, combine and merge are the dense kernel's;
@@ -165,6 +167,102 @@ extern "C" void paged_decode_rope_cache_fp8kv_launch(
                      (const float*)cos_t, (const float*)sin_t,
                      (const int*)pos_dev, B, Hq, Hkv, num_pages, logP, M,
                      rope_rows);
+}
+
+// ---- ragged prefill side: rope + quantising append for packed tokens -------
+// paged_prefill_rope_cache_kernel (paged_attn.hip) for fp8 pools: qkv
+// [T, (Hq+2*Hkv)*128], token t at logical position pos[t], its K/V row at
+// physical pool row slot[t]. Same lane map (8 lanes per (token, head), lane
+// i8 owns the rotation pairs (8*i8 + j, 64 + 8*i8 + j)) and the same
+// rotation expression, so q is that kernel's q bit for bit. A k head is
+// roped and rounded to bf16, a v head taken raw; the row's amax is an
+// 8-lane butterfly over the lane's 16 elements, and the 16 bytes go out as
+// two 8-byte stores, lane 0 of the 8 adding the scale: quantize_kv_rows of
+// the row the bf16 kernel would store. pos is clamped to the rope table,
+// slot to [0, num_pages * P), offsets are 64-bit.
+__global__ void __launch_bounds__(256)
+paged_prefill_rope_cache_fp8kv_kernel(
+    const unsigned short* __restrict__ qkv,
+    unsigned short* __restrict__ qout,  // [T,Hq,128]
+    unsigned char* __restrict__ k8pool, unsigned char* __restrict__ v8pool,
+    float* __restrict__ kspool, float* __restrict__ vspool,
+    const float* __restrict__ cos_t,   // [R, 64]
+    const float* __restrict__ sin_t,
+    const int* __restrict__ pos_dev,   // [T]
+    const int* __restrict__ slot_dev,  // [T]
+    long T, int Hq, int Hkv, long pool_rows, int rope_rows) {
+  const int nh = Hq + 2 * Hkv;
+  const long n = T * nh * 8;  // whole 8-lane groups enter and leave together
+  for (long i = grid_stride_begin(); i < n; i += grid_stride()) {
+    const int i8 = (int)(i & 7);
+    const long th = i >> 3;
+    const long t = th / nh;
+    const int h = (int)(th - t * nh);
+    const unsigned short* src = qkv + th * HD + i8 * 8;
+    ushort8 u1 = *(const ushort8*)src;
+    ushort8 u2 = *(const ushort8*)(src + 64);
+    if (h < Hq + Hkv) {  // q or k head: rotate, round to bf16
+      const int pos = min(max(pos_dev[t], 0), rope_rows - 1);
+      const float* cp = cos_t + (long)pos * 64 + i8 * 8;
+      const float* sp = sin_t + (long)pos * 64 + i8 * 8;
+      const f32x4 c0 = *(const f32x4*)cp, c1 = *(const f32x4*)(cp + 4);
+      const f32x4 s0 = *(const f32x4*)sp, s1 = *(const f32x4*)(sp + 4);
+      ushort8 o1, o2;
+      #pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const float c = j < 4 ? c0[j & 3] : c1[j & 3];
+        const float s = j < 4 ? s0[j & 3] : s1[j & 3];
+        const float x1 = bf16_to_f32(u1[j]);
+        const float x2 = bf16_to_f32(u2[j]);
+        o1[j] = f32_to_bf16(fmaf(x1, c, -s * x2));
+        o2[j] = f32_to_bf16(fmaf(x2, c, s * x1));
+      }
+      u1 = o1;
+      u2 = o2;
+    }
+    if (h < Hq) {
+      unsigned short* dst = qout + (t * Hq + h) * HD + i8 * 8;
+      *(ushort8*)dst = u1;
+      *(ushort8*)(dst + 64) = u2;
+      continue;
+    }
+    float x1[8], x2[8];
+    float amax = 0.f;
+    #pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      x1[j] = bf16_to_f32(u1[j]);
+      x2[j] = bf16_to_f32(u2[j]);
+      amax = fmaxf(amax, fmaxf(fabsf(x1[j]), fabsf(x2[j])));
+    }
+    #pragma unroll
+    for (int off = 4; off >= 1; off >>= 1)
+      amax = fmaxf(amax, __shfl_xor(amax, off, 8));
+    const float scale = kv_row_scale(amax);
+    const bool is_k = h < Hq + Hkv;
+    const long slot = min(max((long)slot_dev[t], 0L), pool_rows - 1);
+    const long drow = slot * Hkv + (is_k ? h - Hq : h - Hq - Hkv);
+    unsigned char* dst = (is_k ? k8pool : v8pool) + drow * HD + i8 * 8;
+    *(uint2_v*)dst = kv_quant_pack8(x1, scale);
+    *(uint2_v*)(dst + 64) = kv_quant_pack8(x2, scale);
+    if (i8 == 0) (is_k ? kspool : vspool)[drow] = scale;
+  }
+}
+
+extern "C" void paged_prefill_rope_cache_fp8kv_launch(
+    const void* qkv, void* qout, void* k8pool, void* v8pool, void* kspool,
+    void* vspool, const void* cos_t, const void* sin_t, const void* pos_dev,
+    const void* slot_dev, long T, int Hq, int Hkv, long pool_rows,
+    int rope_rows, hipStream_t stream) {
+  const long n = T * (Hq + 2 * Hkv) * 8;
+  long grid = (n + 255) / 256;
+  if (grid > 65535 * 8) grid = 65535 * 8;
+  hipLaunchKernelGGL(paged_prefill_rope_cache_fp8kv_kernel,
+                     dim3((unsigned)grid), dim3(256), 0, stream,
+                     (const unsigned short*)qkv, (unsigned short*)qout,
+                     (unsigned char*)k8pool, (unsigned char*)v8pool,
+                     (float*)kspool, (float*)vspool, (const float*)cos_t,
+                     (const float*)sin_t, (const int*)pos_dev,
+                     (const int*)slot_dev, T, Hq, Hkv, pool_rows, rope_rows);
 }
 
 // ---- prefill side: quantise S rows of K and V into the pages ---------------
