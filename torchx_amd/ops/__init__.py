@@ -165,10 +165,17 @@ class _RoPE(torch.autograd.Function):
 
 
 def rope(x: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor) -> torch.Tensor:
-    """x: [B, S, H, D] bf16; rotate-half (Llama) convention."""
+    """x: [B, S, H, D] bf16; rotate-half (Llama) convention. cos/sin are
+    f32 [>= S, D/2] tables; position s uses row s."""
     heads = x.shape[2]
     if _on_gpu(x):
-        return _RoPE.apply(x, cos, sin, heads)
+        # the kernel takes a row's position modulo the table length, so it
+        # gets exactly the S rows this x uses
+        S = x.shape[1]
+        if cos.shape[0] < S or sin.shape[0] < S:
+            raise ValueError(
+                f"rope: tables of {cos.shape[0]} rows for a sequence of {S}")
+        return _RoPE.apply(x, cos[:S], sin[:S], heads)
     return reference.rope(x, cos, sin)
 
 
@@ -180,8 +187,9 @@ def rope(x: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor) -> torch.Tensor:
 class _SwiGLU(torch.autograd.Function):
     @staticmethod
     def forward(ctx, g: torch.Tensor, u: torch.Tensor):
+        g, u = g.contiguous(), u.contiguous()
         ctx.save_for_backward(g, u)
-        return hip_ops().swiglu_fwd(g.contiguous(), u.contiguous())
+        return hip_ops().swiglu_fwd(g, u)
 
     @staticmethod
     def backward(ctx, dout: torch.Tensor):
@@ -206,7 +214,8 @@ class _CrossEntropy(torch.autograd.Function):
     def forward(ctx, logits: torch.Tensor, targets: torch.Tensor):
         V = logits.shape[-1]
         logits2d = logits.contiguous().view(-1, V)
-        loss, lse = hip_ops().ce_fwd(logits2d, targets.contiguous().view(-1))
+        targets = targets.contiguous().view(-1)
+        loss, lse = hip_ops().ce_fwd(logits2d, targets)
         ctx.save_for_backward(logits2d, targets, lse)
         ctx.orig_shape = logits.shape
         return loss.mean()
@@ -216,11 +225,16 @@ class _CrossEntropy(torch.autograd.Function):
         logits2d, targets, lse = ctx.saved_tensors
         T = logits2d.shape[0]
         gscale = (gout.float() / T).expand(T).contiguous()
-        dlogits = hip_ops().ce_bwd(logits2d, targets.view(-1), lse, gscale)
+        dlogits = hip_ops().ce_bwd(logits2d, targets, lse, gscale)
         return dlogits.view(ctx.orig_shape), None
 
 
 def cross_entropy(logits: torch.Tensor, targets: torch.Tensor) -> torch.Tensor:
+    """Mean cross entropy of logits [..., V] bf16 against int64 targets.
+    ``ignore_index`` is not supported on the GPU path: every target must lie
+    in [0, V). A target outside it (torch's default -100 included, which
+    the CPU path skips) gives that row a NaN loss, and with it a NaN mean;
+    its dlogits row is the plain softmax."""
     if _on_gpu(logits):
         return _CrossEntropy.apply(logits, targets)
     return reference.cross_entropy(logits, targets)

@@ -159,6 +159,14 @@ void check_f32(const at::Tensor& t, const char* name) {
   TORCH_CHECK(t.is_contiguous(), name, " must be contiguous");
 }
 
+// cross-entropy targets: one int64 class index per row of the logits
+void check_targets(const at::Tensor& t, long T) {
+  TORCH_CHECK(t.is_cuda(), "targets must be on GPU");
+  TORCH_CHECK(t.scalar_type() == at::kLong, "targets must be int64");
+  TORCH_CHECK(t.is_contiguous(), "targets must be contiguous");
+  TORCH_CHECK(t.numel() == T, "targets must have one element per row");
+}
+
 }  // namespace
 
 // ---- RMSNorm --------------------------------------------------------------
@@ -167,6 +175,7 @@ std::vector<at::Tensor> rmsnorm_fwd(at::Tensor x, at::Tensor w, double eps) {
   check_bf16(w, "w");
   const long H = x.size(-1);
   TORCH_CHECK(H % 2048 == 0 && H <= 8192, "rmsnorm: H must be k*2048, <=8192");
+  TORCH_CHECK(w.numel() == H, "w size mismatch");
   const long rows = x.numel() / H;
   auto y = at::empty_like(x);
   auto invrms = at::empty({rows}, x.options().dtype(at::kFloat));
@@ -216,8 +225,15 @@ at::Tensor rope(at::Tensor x, at::Tensor cos_t, at::Tensor sin_t, long heads,
   check_f32(sin_t, "sin");
   const long D = x.size(-1);
   const long rows = x.numel() / D;
+  TORCH_CHECK(D % 8 == 0, "rope: head_dim must be a multiple of 8");
+  TORCH_CHECK(cos_t.dim() == 2 && cos_t.size(1) == D / 2,
+              "cos table must be [S, D/2]");
+  TORCH_CHECK(sin_t.sizes() == cos_t.sizes(), "sin table must match cos");
   const long S = cos_t.size(0);
-  TORCH_CHECK(cos_t.size(1) == D / 2, "cos table must be [S, D/2]");
+  // rows are [.., S, heads]: the position of a row is (row / heads) % S,
+  // which is only the sequence index if x holds whole [S, heads, D] blocks
+  TORCH_CHECK(heads > 0 && S > 0 && x.numel() % (heads * S * D) == 0,
+              "rope: x must be [.., S, heads, D] for a table of S rows");
   auto y = at::empty_like(x);
   rope_launch(x.data_ptr(), y.data_ptr(), cos_t.data_ptr(), sin_t.data_ptr(),
               rows, (int)D, (int)heads, (int)S, (float)sign, cur_stream());
@@ -228,6 +244,7 @@ at::Tensor rope(at::Tensor x, at::Tensor cos_t, at::Tensor sin_t, long heads,
 at::Tensor swiglu_fwd(at::Tensor g, at::Tensor u) {
   check_bf16(g, "g");
   check_bf16(u, "u");
+  TORCH_CHECK(u.numel() == g.numel(), "swiglu: g / u size mismatch");
   auto out = at::empty_like(g);
   swiglu_fwd_launch(g.data_ptr(), u.data_ptr(), out.data_ptr(), g.numel(),
                     cur_stream());
@@ -237,6 +254,10 @@ at::Tensor swiglu_fwd(at::Tensor g, at::Tensor u) {
 std::vector<at::Tensor> swiglu_bwd(at::Tensor dout, at::Tensor g,
                                    at::Tensor u) {
   check_bf16(dout, "dout");
+  check_bf16(g, "g");
+  check_bf16(u, "u");
+  TORCH_CHECK(dout.numel() == g.numel() && u.numel() == g.numel(),
+              "swiglu: dout / g / u size mismatch");
   auto dg = at::empty_like(g);
   auto du = at::empty_like(u);
   swiglu_bwd_launch(dout.data_ptr(), g.data_ptr(), u.data_ptr(), dg.data_ptr(),
@@ -251,8 +272,13 @@ void adamw_step(at::Tensor p32, at::Tensor p16, at::Tensor g, at::Tensor m,
   check_f32(p32, "p32");
   check_bf16(p16, "p16");
   check_bf16(g, "g");
+  check_f32(m, "m");
+  check_f32(v, "v");
   const long n = p32.numel();
   TORCH_CHECK(n % 4 == 0, "adamw: n must be a multiple of 4");
+  TORCH_CHECK(p16.numel() == n && g.numel() == n && m.numel() == n &&
+                  v.numel() == n,
+              "adamw: p32 / p16 / g / m / v size mismatch");
   const float bc1 = 1.0f - powf((float)beta1, (float)step);
   const float bc2 = 1.0f - powf((float)beta2, (float)step);
   adamw_launch(p32.data_ptr(), p16.data_ptr(), g.data_ptr(), m.data_ptr(),
@@ -263,9 +289,9 @@ void adamw_step(at::Tensor p32, at::Tensor p16, at::Tensor g, at::Tensor m,
 // ---- Cross entropy --------------------------------------------------------
 std::vector<at::Tensor> ce_fwd(at::Tensor logits, at::Tensor targets) {
   check_bf16(logits, "logits");
-  TORCH_CHECK(targets.scalar_type() == at::kLong, "targets must be int64");
   const long V = logits.size(-1);
   const long T = logits.numel() / V;
+  check_targets(targets, T);
   auto loss = at::empty({T}, logits.options().dtype(at::kFloat));
   auto lse = at::empty({T}, logits.options().dtype(at::kFloat));
   ce_fwd_launch(logits.data_ptr(), targets.data_ptr(), loss.data_ptr(),
@@ -280,6 +306,9 @@ at::Tensor ce_bwd(at::Tensor logits, at::Tensor targets, at::Tensor lse,
   check_f32(gscale, "gscale");
   const long V = logits.size(-1);
   const long T = logits.numel() / V;
+  check_targets(targets, T);
+  TORCH_CHECK(lse.numel() == T && gscale.numel() == T,
+              "lse / gscale must have one element per row");
   auto dlogits = at::empty_like(logits);
   ce_bwd_launch(logits.data_ptr(), targets.data_ptr(), lse.data_ptr(),
                 gscale.data_ptr(), dlogits.data_ptr(), T, (int)V,
@@ -448,9 +477,13 @@ at::Tensor rope_qkv(at::Tensor x, at::Tensor cos_t, at::Tensor sin_t,
   check_bf16(x, "x");
   check_f32(cos_t, "cos");
   check_f32(sin_t, "sin");
+  TORCH_CHECK(x.dim() == 3, "qkv must be [B, S, (Hq + 2 Hkv) * 128]");
   const int B = x.size(0), S = x.size(1);
   const long rs = (Hq + 2 * Hkv) * 128;
   TORCH_CHECK(x.size(2) == rs, "qkv last dim mismatch");
+  TORCH_CHECK(cos_t.dim() == 2 && cos_t.size(0) >= S && cos_t.size(1) == 64,
+              "cos table must be [>= S, 64]");
+  TORCH_CHECK(sin_t.sizes() == cos_t.sizes(), "sin table must match cos");
   at::Tensor y = inplace ? x : at::empty_like(x);
   rope_qkv_launch(x.data_ptr(), y.data_ptr(), cos_t.data_ptr(),
                   sin_t.data_ptr(), (long)B * S, (int)(Hq + Hkv), rs, S,
@@ -478,9 +511,13 @@ at::Tensor swiglu_gu_fwd(at::Tensor gu) {
 
 at::Tensor swiglu_gu_bwd(at::Tensor dout, at::Tensor gu) {
   check_bf16(dout, "dout");
+  check_bf16(gu, "gu");
   const long twoI = gu.size(-1);
+  TORCH_CHECK(twoI % 16 == 0, "gu last dim must be 2I, I % 8 == 0");
   const long I = twoI / 2;
   const long rows = gu.numel() / twoI;
+  TORCH_CHECK(dout.numel() == rows * I && dout.size(-1) == I,
+              "swiglu_gu_bwd: dout must be [rows, I]");
   auto dgu = at::empty_like(gu);
   swiglu_gu_bwd_launch(dout.data_ptr(), gu.data_ptr(), dgu.data_ptr(), rows,
                        I, cur_stream());

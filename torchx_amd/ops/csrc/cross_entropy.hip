@@ -63,7 +63,10 @@ ce_fwd_kernel(const unsigned short* __restrict__ logits,  // [T, V]
     for (int i = 1; i < 4; ++i) ce_combine(M, S, red_m[i], red_s[i]);
     float l = M + __logf(S);
     lse[row] = l;
-    loss[row] = l - tgt_val;
+    // tgt_val was written only if some column equals the target: a target
+    // outside [0, V) (ignore_index included) has no loss -> quiet NaN
+    loss[row] = (tgt >= 0 && tgt < V) ? l - tgt_val
+                                      : __int_as_float(0x7fc00000);
   }
 }
 

@@ -70,13 +70,14 @@ extern "C" void rope_launch(
 }
 
 // ---------------------------------------------------------------------------
-// SwiGLU: out = silu(g) * u   (all bf16, flat n elements, n % 8 == 0)
+// SwiGLU: out = silu(g) * u   (all bf16, flat n elements; the last n % 8
+// go through a scalar loop with the vector loop's per-element expressions)
 // ---------------------------------------------------------------------------
 __global__ void swiglu_fwd_kernel(
     const unsigned short* __restrict__ g,
     const unsigned short* __restrict__ u,
     unsigned short* __restrict__ out,
-    long n8) {
+    long n8, long n) {
   for (long i8 = grid_stride_begin(); i8 < n8; i8 += grid_stride()) {
     long i = i8 * 8;
     ushort8 gv = *(const ushort8*)(g + i);
@@ -92,6 +93,13 @@ __global__ void swiglu_fwd_kernel(
     }
     *(ushort8*)(out + i) = ov;
   }
+  // tail
+  for (long i = n8 * 8 + grid_stride_begin(); i < n; i += grid_stride()) {
+    float gf = bf16_to_f32(g[i]);
+    float uf = bf16_to_f32(u[i]);
+    float sig = 1.0f / (1.0f + __builtin_amdgcn_exp2f(-1.44269504f * gf));
+    out[i] = f32_to_bf16(gf * sig * uf);
+  }
 }
 
 __global__ void swiglu_bwd_kernel(
@@ -100,7 +108,7 @@ __global__ void swiglu_bwd_kernel(
     const unsigned short* __restrict__ u,
     unsigned short* __restrict__ dg,
     unsigned short* __restrict__ du,
-    long n8) {
+    long n8, long n) {
   for (long i8 = grid_stride_begin(); i8 < n8; i8 += grid_stride()) {
     long i = i8 * 8;
     ushort8 dov = *(const ushort8*)(dout + i);
@@ -122,6 +130,17 @@ __global__ void swiglu_bwd_kernel(
     *(ushort8*)(dg + i) = dgv;
     *(ushort8*)(du + i) = duv;
   }
+  // tail
+  for (long i = n8 * 8 + grid_stride_begin(); i < n; i += grid_stride()) {
+    float dof = bf16_to_f32(dout[i]);
+    float gf = bf16_to_f32(g[i]);
+    float uf = bf16_to_f32(u[i]);
+    float sig = 1.0f / (1.0f + __builtin_amdgcn_exp2f(-1.44269504f * gf));
+    float silu = gf * sig;
+    float dsilu = sig * (1.0f + gf * (1.0f - sig));
+    dg[i] = f32_to_bf16(dof * uf * dsilu);
+    du[i] = f32_to_bf16(dof * silu);
+  }
 }
 
 extern "C" void swiglu_fwd_launch(const void* g, const void* u, void* out,
@@ -133,7 +152,7 @@ extern "C" void swiglu_fwd_launch(const void* g, const void* u, void* out,
   if (grid == 0) grid = 1;
   hipLaunchKernelGGL(swiglu_fwd_kernel, dim3((int)grid), dim3(block), 0,
                      stream, (const unsigned short*)g,
-                     (const unsigned short*)u, (unsigned short*)out, n8);
+                     (const unsigned short*)u, (unsigned short*)out, n8, n);
 }
 
 extern "C" void swiglu_bwd_launch(const void* dout, const void* g,
@@ -147,7 +166,7 @@ extern "C" void swiglu_bwd_launch(const void* dout, const void* g,
   hipLaunchKernelGGL(swiglu_bwd_kernel, dim3((int)grid), dim3(block), 0,
                      stream, (const unsigned short*)dout,
                      (const unsigned short*)g, (const unsigned short*)u,
-                     (unsigned short*)dg, (unsigned short*)du, n8);
+                     (unsigned short*)dg, (unsigned short*)du, n8, n);
 }
 
 // ---------------------------------------------------------------------------
