@@ -222,6 +222,11 @@ def main():
                         "expert GEMV kernels (fused) or the per-expert loop "
                         "with one host sync per layer (loop); default: "
                         "TORCHX_AMD_MOE_DECODE, else fused")
+    p.add_argument("--moe-router", choices=["torch", "fused"], default=None,
+                   help="Mixtral decode routing: router matmul + torch.topk "
+                        "+ softmax (torch) or the one-kernel rmsnorm + router "
+                        "of moe_route.hip (fused); default: "
+                        "TORCHX_AMD_MOE_ROUTER, else torch")
     p.add_argument("--weights", choices=["bf16", "fp8"], default="bf16",
                    help="decode weights of the block linears (Mixtral: "
                         "attention linears and experts): bf16, or fp8 e4m3 "
@@ -253,6 +258,10 @@ def main():
         from torchx_amd import ops
 
         ops.set_moe_decode_impl(args.moe_decode)
+    if args.moe_router is not None:
+        from torchx_amd import ops
+
+        ops.set_moe_router_impl(args.moe_router)
     if args.admit_many:
         args.batcher = True
     if args.paged and args.graph:
@@ -376,6 +385,7 @@ def main():
         "kv_dtype": args.kv_cache,
         "page_size": args.page_size if args.paged else None,
         "moe_decode": ops.get_moe_decode_impl() if moe else None,
+        "moe_router": ops.get_moe_router_impl() if moe else None,
     }))
     return 0
 

@@ -12,7 +12,15 @@ call finds its weights in the last-level cache.
 ``--step``: mixtral_8x7b, prompt 512, B = 1, 4, 8: decode steps with bf16
 and with fp8 decode weights alternated in one process on the same caches
 (4 warm + 48 timed steps from position 512 each, host clock around a
-device synchronise), median [min..max] of three rounds."""
+device synchronise), median [min..max] of three rounds. With ``--router``
+every weight kind runs under the "torch" and the "fused" MoE router
+(``ops.set_moe_router_impl``), the four alternated.
+
+``--router`` alone: kernel level of the fused router (moe_route.hip),
+H 4096, E 8, k 2 at B = 1, 4, 8: ``rmsnorm_res_route`` against the
+sequence it replaces (``rmsnorm_res`` + router matmul, ``.float()``,
+``topk``, ``softmax``, ``.to``) and against ``rmsnorm_res`` alone,
+alternated, device events, median [min..max] of the rounds."""
 
 import argparse
 import os
@@ -94,7 +102,46 @@ def kernel_level(args):
     return 0
 
 
+def router_level(args):
+    from torchx_amd import ops
+
+    dev = torch.device("cuda:0")
+    H, E, k = args.hidden, 8, 2
+    bf = torch.bfloat16
+    torch.manual_seed(0)
+    w = (0.75 + 0.5 * torch.rand(H, device=dev)).to(bf)
+    wr = (0.02 * torch.randn(E, H, device=dev)).to(bf)
+    for B in (1, 4, 8):
+        x = torch.randn(B, H, device=dev, dtype=bf)
+        a = torch.randn(B, H, device=dev, dtype=bf)
+
+        def parent():
+            _, y = ops.rmsnorm_res(x, a, w, 1e-5)
+            logits = (y @ wr.t()).float()
+            v, idx = torch.topk(logits, k, dim=-1)
+            return idx, torch.softmax(v, dim=-1).to(bf)
+
+        fns = {
+            "rmsnorm_res alone": lambda: ops.rmsnorm_res(x, a, w, 1e-5),
+            "rmsnorm_res + torch router": parent,
+            "rmsnorm_res_route": lambda: ops.rmsnorm_res_route(
+                x, a, w, 1e-5, wr, k),
+        }
+        ts = {tag: [] for tag in fns}
+        for _ in range(args.rounds):
+            for tag, fn in fns.items():
+                ts[tag].append(time_fn(fn, args.iters))
+        print(f"B={B} H={H} E={E} k={k}")
+        for tag, t in ts.items():
+            t = sorted(t)
+            print(f"  {tag:27s} {t[len(t) // 2]:7.2f} us "
+                  f"[{t[0]:.2f}..{t[-1]:.2f}]", flush=True)
+    return 0
+
+
 def step_level(args):
+    from torchx_amd import ops
+
     from torchx_amd.models.generate import (
         KVCache, decode_step, prefill, quantize_decode_weights,
     )
@@ -122,10 +169,13 @@ def step_level(args):
         caches = [KVCache.empty(cfg, B, S0 + warm + steps + 8, dev)
                   for _ in range(cfg.num_layers)]
         first = prefill(model, tokens, caches).argmax(-1, keepdim=True)
-        ms = {"bf16": [], "fp8": []}
+        routers = ("torch", "fused") if args.router else (None,)
+        ms = {(wk, r): [] for wk in ("bf16", "fp8") for r in routers}
         for _ in range(3):
             for mode in ms:
-                use(mode)
+                use(mode[0])
+                if mode[1] is not None:
+                    ops.set_moe_router_impl(mode[1])
                 for c in caches:
                     c.length = S0
                 nxt = first
@@ -143,23 +193,35 @@ def step_level(args):
         for mode, t in ms.items():
             t = sorted(t)
             med[mode] = t[1]
-            print(f"B={B} {mode:4s} {t[1]:7.3f} ms/step [{t[0]:.3f}.."
+            tag = mode[0] + (f" router={mode[1]}" if mode[1] else "")
+            print(f"B={B} {tag:17s} {t[1]:7.3f} ms/step [{t[0]:.3f}.."
                   f"{t[2]:.3f}]  {B / t[1] * 1e3:7.1f} tok/s", flush=True)
-        print(f"B={B} fp8 / bf16 time {med['fp8'] / med['bf16']:.3f}",
-              flush=True)
+        for r in routers:
+            print(f"B={B} fp8 / bf16 time"
+                  + (f" router={r}" if r else "")
+                  + f" {med['fp8', r] / med['bf16', r]:.3f}", flush=True)
+        if args.router:
+            for wk in ("bf16", "fp8"):
+                print(f"B={B} {wk} fused / torch router time "
+                      f"{med[wk, 'fused'] / med[wk, 'torch']:.3f}",
+                      flush=True)
+    ops.set_moe_router_impl("torch")
     return 0
 
 
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--step", action="store_true")
+    p.add_argument("--router", action="store_true")
     p.add_argument("--hidden", type=int, default=4096)
     p.add_argument("--inter", type=int, default=14336)
     p.add_argument("--sets", type=int, default=4)
     p.add_argument("--rounds", type=int, default=3)
     p.add_argument("--iters", type=int, default=100)
     args = p.parse_args()
-    return step_level(args) if args.step else kernel_level(args)
+    if args.step:
+        return step_level(args)
+    return router_level(args) if args.router else kernel_level(args)
 
 
 if __name__ == "__main__":

@@ -544,7 +544,10 @@ def decode_step(model, token: torch.Tensor, caches: list,
     kernels (see PagedBatcher). A Mixtral model runs the same step with
     its active-expert MLP half (``_mlp_decode``), which is
     position-independent; its routing reads the device, so only the
-    dense model's step is capturable. ``Fp8KVCache`` caches take all three
+    dense model's step is capturable. Under
+    ``ops.set_moe_router_impl("fused")`` that half is three dispatches:
+    ``ops.rmsnorm_res_route`` (norm, router GEMV, top-k and softmax in one
+    kernel) and the two of ``ops.moe_decode_mlp``. ``Fp8KVCache`` caches take all three
     ``pos`` forms through the fp8 KV kernels (quantising append, GQA-shared
     attention), ``Fp8PagedKVCache`` caches the [B] vector through their
     block-table forms; ``rows_hint`` is a host bound on ``pos + 1`` that
@@ -597,8 +600,12 @@ def decode_step(model, token: torch.Tensor, caches: list,
                 # (continuous batching) — each row attends its own length
                 o = ops.decode_attention_dev(q, cache.k, cache.v, pos_dev)
         a = ops.decode_linear(o.reshape(B, -1), _decode_w(blk.wo))
-        x, xn = ops.rmsnorm_res(x, a, blk.mlp_norm, cfg.rms_eps)
-        m = _mlp_decode(blk, xn)
+        if "moe" in blk._modules and ops.get_moe_router_impl() == "fused":
+            from .generate_moe import _moe_norm_mlp_decode
+            x, m = _moe_norm_mlp_decode(blk, x, a, cfg.rms_eps)
+        else:
+            x, xn = ops.rmsnorm_res(x, a, blk.mlp_norm, cfg.rms_eps)
+            m = _mlp_decode(blk, xn)
         w_next = (blocks[i + 1].attn_norm if i + 1 < len(blocks)
                   else model.final_norm)
         x, xn = ops.rmsnorm_res(x, m, w_next, cfg.rms_eps)

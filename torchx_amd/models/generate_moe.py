@@ -14,8 +14,11 @@ layer). Router, top-k and softmax run on the device and
 ``ops.moe_decode_mlp`` reads their result there: its two grouped expert
 GEMV kernels (ops/csrc/moe_gemv.hip) are the whole MLP half, with no
 host sync (``ops.set_moe_decode_impl("loop")`` brings back the
-per-expert loop with its one sync per layer; same bits). In prefill the
-MLP half is the training ``MoELayer`` itself.
+per-expert loop with its one sync per layer; same bits).
+``ops.set_moe_router_impl("fused")`` moves router, top-k and softmax into
+the kernel of the norm in front of them (``ops.rmsnorm_res_route``,
+ops/csrc/moe_route.hip). In prefill the MLP half is the training
+``MoELayer`` itself.
 
 Single-rank serving only (``ep_size == 1`` — all experts local); the
 expert-parallel all-to-all path in models/mixtral.py is a training
@@ -66,6 +69,19 @@ def _moe_mlp_decode(moe: MoELayer, x: torch.Tensor) -> torch.Tensor:
     w, idx = torch.topk(logits, cfg.top_k, dim=-1)
     w = torch.softmax(w, dim=-1).to(x.dtype)              # [B, k]
     return ops.moe_decode_mlp(x, idx, w, *_expert_weights(moe))
+
+
+def _moe_norm_mlp_decode(blk, x: torch.Tensor, a: torch.Tensor, eps: float):
+    """``decode_step``'s residual add + MLP norm + MoE MLP of a Mixtral
+    block under ``ops.set_moe_router_impl("fused")``: x, a [B, H] -> (the
+    new residual stream, the MLP output). Three dispatches: the norm and
+    the routing are one kernel (fp32 logits, ties to the lower expert),
+    which ``ops.moe_decode_mlp`` reads on the device."""
+    moe = blk.moe
+    assert moe.ep_size == 1, "serving path is single-rank (all experts local)"
+    x, xn, idx, cw = ops.rmsnorm_res_route(x, a, blk.mlp_norm, eps,
+                                           moe.router.weight, moe.cfg.top_k)
+    return x, ops.moe_decode_mlp(xn, idx, cw, *_expert_weights(moe))
 
 
 # the shared passes tell a MixtralBlock from a LlamaBlock themselves

@@ -1471,3 +1471,73 @@ def moe_decode_mlp(x: torch.Tensor, idx: torch.Tensor, cw: torch.Tensor,
         h = hip.moe_gemv_swiglu(x, idx, list(wgu))
         return hip.moe_gemv_down_combine(h, idx, cw, list(wdown))
     return moe_decode_mlp_loop(x, idx, cw, wgu, wdown)
+
+
+# ---------------------------------------------------------------------------
+# MoE decode router (serving): gate GEMV + top-k + softmax in one kernel,
+# alone or behind the residual add + RMSNorm that feeds it —
+# ops/csrc/moe_route.hip. fp32 logits, ties to the lower expert index, a
+# row's result independent of the batch it is in.
+# ---------------------------------------------------------------------------
+
+_MOE_ROUTER_IMPLS = ("torch", "fused")
+_moe_router_impl = os.environ.get("TORCHX_AMD_MOE_ROUTER", "torch")
+assert _moe_router_impl in _MOE_ROUTER_IMPLS, (
+    f"TORCHX_AMD_MOE_ROUTER must be one of {_MOE_ROUTER_IMPLS}")
+
+
+def set_moe_router_impl(impl: str) -> None:
+    """Select the routing of the Mixtral decode step: "torch" (default; the
+    router matmul, ``torch.topk`` and ``softmax`` on bf16-rounded logits)
+    or "fused" (``rmsnorm_res_route``: one kernel for norm and routing,
+    fp32 logits). The two can pick different experts at a near-tie. The
+    initial value comes from TORCHX_AMD_MOE_ROUTER."""
+    global _moe_router_impl
+    if impl not in _MOE_ROUTER_IMPLS:
+        raise ValueError(f"moe router impl must be 'torch' or 'fused', "
+                         f"got {impl!r}")
+    _moe_router_impl = impl
+
+
+def get_moe_router_impl() -> str:
+    return _moe_router_impl
+
+
+def _moe_route_ok(y: torch.Tensor, wr: torch.Tensor, k: int) -> bool:
+    if not (y.is_cuda and y.dim() == 2 and y.dtype == torch.bfloat16
+            and wr.dim() == 2 and wr.dtype == torch.bfloat16
+            and wr.device == y.device and wr.is_contiguous()):
+        return False
+    B, H = y.shape
+    E = wr.shape[0]
+    return B >= 1 and wr.shape[1] == H and H % 2048 == 0 \
+        and 2048 <= H <= 8192 and 1 <= E <= 16 and 1 <= k <= min(8, E)
+
+
+def moe_route(y: torch.Tensor, wr: torch.Tensor, k: int):
+    """Top-k routing of a decode micro-batch: y [B, H] bf16 (normed
+    activations), router weight ``wr`` [E, H] bf16 -> ``(idx, cw)``, [B, k]
+    int64 and bf16, the layout ``moe_decode_mlp`` reads: the k largest fp32
+    logits in descending order, ties to the lower expert index, and their
+    softmax. One dispatch on the GPU for H a multiple of 2048 up to 8192,
+    E <= 16 and k <= min(8, E); the CPU and every other shape run
+    ``reference.moe_route``, which defines the result."""
+    if _moe_route_ok(y, wr, k):
+        idx, cw = hip_ops().moe_route(y.contiguous(), wr, k)
+        return idx, cw
+    return reference.moe_route(y, wr, k)
+
+
+def rmsnorm_res_route(x: torch.Tensor, res: Optional[torch.Tensor],
+                      w: torch.Tensor, eps: float, wr: torch.Tensor, k: int):
+    """``rmsnorm_res`` and ``moe_route`` on its output in one dispatch:
+    returns ``(s, y, idx, cw)``. ``s`` and ``y`` are the bits of
+    ``rmsnorm_res``; the normed row goes from the norm to the router dot
+    products in registers. Inference only."""
+    if _moe_route_ok(x, wr, k):
+        s, y, idx, cw = hip_ops().rmsnorm_res_route(
+            x.contiguous(), res.contiguous() if res is not None else None,
+            w.contiguous(), eps, wr, k)
+        return s, y, idx, cw
+    s, y = rmsnorm_res(x, res, w, eps)
+    return (s, y, *reference.moe_route(y, wr, k))

@@ -33,18 +33,20 @@ SOURCES = [
     "gemm_fp8w_mfma.hip",
     "moe_gemv.hip",
     "moe_gemv_fp8.hip",
+    "moe_route.hip",
     "fp8_cast.hip",
     "probe.hip",
     "bindings.cpp",
 ]
 
-# per-source extra flags: moe_gemv.hip, the fp8-weight kernels and the fp8
+# per-source extra flags: moe_gemv.hip, moe_route.hip, the fp8-weight kernels and the fp8
 # KV-cache kernels keep their fp32 arithmetic on the scalar VALU forms (no
 # packed-fp32 instructions); the KV quantisers are held to torch bit for bit
 _NO_PK_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 EXTRA_FLAGS = {
     "moe_gemv.hip": _NO_PK_F32,
     "moe_gemv_fp8.hip": _NO_PK_F32,
+    "moe_route.hip": _NO_PK_F32,
     "gemv_fp8.hip": _NO_PK_F32,
     "gemm_fp8w_mfma.hip": _NO_PK_F32,
     "decode_attn_fp8kv.hip": _NO_PK_F32,

@@ -89,6 +89,9 @@ void gemm_fp8w_mfma_launch(const void*, const void*, const void*, void*, int,
                            int, int, int, hipStream_t);
 void gemm_swiglu_fp8w_mfma_launch(const void*, const void*, const void*, void*,
                                   int, int, int, hipStream_t);
+void moe_route_launch(const void*, const void*, const void*, const void*,
+                      void*, void*, void*, void*, long, int, int, int, float,
+                      bool, hipStream_t);
 void moe_gemv_swiglu_launch(const void*, const void*, const void* const*,
                             void*, int, int, int, int, int, hipStream_t);
 void moe_gemv_down_combine_launch(const void*, const void*, const void*,
@@ -1607,6 +1610,69 @@ std::vector<at::Tensor> rmsnorm_res(at::Tensor x,
   return {s, y};
 }
 
+// ---- fused MoE decode router (moe_route.hip) --------------------------------
+// idx [B, k] int64 (value descending, ties to the lower expert) and
+// cw [B, k] bf16 (softmax over the k fp32 logits) from y [B, H] and the
+// router weight wr [E, H]; the first form also runs rmsnorm_res in front,
+// in the same dispatch, and returns (s, y, idx, cw).
+namespace {
+
+void check_route(const at::Tensor& y, const at::Tensor& wr, long k) {
+  check_bf16(y, "y");
+  check_bf16(wr, "wr");
+  TORCH_CHECK(y.dim() == 2 && y.size(0) >= 1, "moe_route: y must be [B, H]");
+  const long H = y.size(1);
+  TORCH_CHECK(H % 2048 == 0 && H >= 2048 && H <= 8192,
+              "moe_route: H must be k*2048, <=8192");
+  TORCH_CHECK(wr.dim() == 2 && wr.size(1) == H, "moe_route: wr must be [E, H]");
+  TORCH_CHECK(wr.device() == y.device(), "moe_route: wr on another device");
+  const long E = wr.size(0);
+  TORCH_CHECK(E >= 1 && E <= 16, "moe_route: E must be 1..16");
+  TORCH_CHECK(k >= 1 && k <= 8 && k <= E, "moe_route: k must be 1..min(8, E)");
+}
+
+}  // namespace
+
+std::vector<at::Tensor> moe_route(at::Tensor y, at::Tensor wr, int64_t k) {
+  check_route(y, wr, k);
+  const long B = y.size(0), H = y.size(1), E = wr.size(0);
+  auto idx = at::empty({B, k}, y.options().dtype(at::kLong));
+  auto cw = at::empty({B, k}, y.options());
+  moe_route_launch(nullptr, nullptr, nullptr, wr.data_ptr(), nullptr,
+                   y.data_ptr(), idx.data_ptr(), cw.data_ptr(), B, (int)H,
+                   (int)E, (int)k, 0.f, false, cur_stream());
+  return {idx, cw};
+}
+
+std::vector<at::Tensor> rmsnorm_res_route(at::Tensor x,
+                                          c10::optional<at::Tensor> res,
+                                          at::Tensor w, double eps,
+                                          at::Tensor wr, int64_t k) {
+  check_route(x, wr, k);
+  check_bf16(w, "w");
+  const long B = x.size(0), H = x.size(1), E = wr.size(0);
+  TORCH_CHECK(w.numel() == H && w.device() == x.device(),
+              "rmsnorm_res_route: w must be [H] on x's device");
+  auto y = at::empty_like(x);
+  at::Tensor s = x;
+  const void* rp = nullptr;
+  void* sp = nullptr;
+  if (res.has_value()) {
+    check_bf16(*res, "res");
+    TORCH_CHECK(res->sizes() == x.sizes() && res->device() == x.device(),
+                "res shape or device mismatch");
+    s = at::empty_like(x);
+    rp = res->data_ptr();
+    sp = s.data_ptr();
+  }
+  auto idx = at::empty({B, k}, x.options().dtype(at::kLong));
+  auto cw = at::empty({B, k}, x.options());
+  moe_route_launch(x.data_ptr(), rp, w.data_ptr(), wr.data_ptr(), sp,
+                   y.data_ptr(), idx.data_ptr(), cw.data_ptr(), B, (int)H,
+                   (int)E, (int)k, (float)eps, true, cur_stream());
+  return {s, y, idx, cw};
+}
+
 // ---- fused residual add + rmsnorm (training) -------------------------------
 // s = bf16(x + delta), y = rmsnorm(s) * w; returns (s, y, invrms) with
 // invrms [rows] f32 saved for rmsnorm_bwd.
@@ -1726,4 +1792,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("paged_prefill_rope_cache_fp8kv", &paged_prefill_rope_cache_fp8kv);
   m.def("rmsnorm_res", &rmsnorm_res,
         py::arg("x"), py::arg("res"), py::arg("w"), py::arg("eps"));
+  m.def("moe_route", &moe_route);
+  m.def("rmsnorm_res_route", &rmsnorm_res_route, py::arg("x"),
+        py::arg("res"), py::arg("w"), py::arg("eps"), py::arg("wr"),
+        py::arg("k"));
 }

@@ -169,3 +169,14 @@ def paged_gather(pool: torch.Tensor, table_row: torch.Tensor,
     n = (length + P - 1) // P
     pages = table_row[:n].long()
     return pool[pages].reshape(1, n * P, *pool.shape[2:])[:, :length]
+
+
+def moe_route(y: torch.Tensor, wr: torch.Tensor, k: int):
+    """The MoE decode routing contract: y [..., H] bf16, router weight
+    wr [E, H] -> (idx [..., k] int64, cw [..., k] in y's dtype). fp32
+    logits from the bf16 operands; the k largest in descending order, ties
+    to the lower expert index (a stable sort); fp32 softmax over the k."""
+    logits = y.float() @ wr.float().t()
+    vals, order = torch.sort(logits, dim=-1, descending=True, stable=True)
+    cw = torch.softmax(vals[..., :k], dim=-1).to(y.dtype)
+    return order[..., :k].contiguous(), cw
